@@ -9,8 +9,14 @@ N > 1 is weak-scaled by default: every rank holds its own config-sized read set 
 on the headline) of the same genome, so the job is N x 10 M reads; --strong splits the
 config's reads over the ranks instead.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (read-sharded, RCCL exchange)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the roofline figures
+come from the kernel events of the timed steps).  --full adds the legs that take runs of their
+own: the per-stage breakdown, the host-input legs, the CPU baseline and, at N > 1, the
+strong-scaled leg.  --dump-outputs DIR writes what the last timed step computed (the arrays
+Session.fetch returns) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -262,6 +268,39 @@ def host_input_legs(sess, buf, off, k, P, steps, warmup):
                                % (buf.size + 8 * len(off))}}
 
 
+DUMP_BUDGET = 60_000_000  # bytes of array data over all dumped files (the files stay under 64 MB)
+
+
+def dump_outputs(path, res):
+    """The last timed step's results as path/<name>.npy: the contig characters (float32) and the
+    contig offsets, link offsets and link codes (float64, exact below 2^53).  The arrays share
+    DUMP_BUDGET, the smallest served first; one past its share is written as a fixed sample:
+    element i of m is taken from the i-th of m equal strata at a position drawn from numpy PCG64
+    seed 0, so two builds given the same arguments dump the same positions.  An empty array
+    gets no file (a graph without links, as the headline's single contig: link_offsets, all
+    zero, says so)."""
+    arrays = [("contig_chars", np.frombuffer(res.contig_bytes, np.uint8), np.float32),
+              ("contig_offsets", res.contig_offsets, np.float64),
+              ("link_offsets", res.link_offsets, np.float64),
+              ("link_codes", res.link_codes, np.float64)]
+    os.makedirs(path, exist_ok=True)
+    for name, a, _ in arrays:
+        if not np.asarray(a).size and os.path.exists(os.path.join(path, name + ".npy")):
+            os.remove(os.path.join(path, name + ".npy"))  # (an earlier run's, into the same DIR)
+    arrays = [t for t in arrays if np.asarray(t[1]).size]
+    rng = np.random.default_rng(0)
+    left = DUMP_BUDGET
+    arrays.sort(key=lambda t: np.asarray(t[1]).size * np.dtype(t[2]).itemsize)  # small arrays whole, first
+    for i, (name, a, dt) in enumerate(arrays):
+        a = np.asarray(a)
+        m = left // (len(arrays) - i) // np.dtype(dt).itemsize
+        left -= min(a.size, m) * np.dtype(dt).itemsize
+        if a.size > m:
+            stride = a.size // m
+            a = a[np.arange(m, dtype=np.int64) * stride + rng.integers(0, stride, m)]
+        np.save(os.path.join(path, name + ".npy"), a.astype(dt))
+
+
 def load_traffic(workload, kernel):
     """HBM bytes per launch of `kernel` from rocprofv3 PMC passes (profiles/traffic_*.json,
     written by profiles/collect_traffic.py; FETCH_SIZE doubled per the gfx950 note)."""
@@ -285,18 +324,24 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="ecoli10m", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's results (contig characters and offsets, link offsets and "
+                         "codes) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: per-stage breakdown, host-input legs, CPU "
+                         "baseline, and at N > 1 the strong-scaled leg")
     ap.add_argument("--cpu-sample-reads", type=int, default=1_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-host-input", action="store_true",
-                    help="skip the host-input legs (reads in pinned host memory, PCIe copy inside the step)")
+                    help="--full: skip the host-input legs (reads in pinned host memory, PCIe copy inside the step)")
     ap.add_argument("--sharded", action="store_true", help="use the multi-GPU path even with one rank")
     ap.add_argument("--strong", action="store_true",
                     help="N > 1: split the config's reads over the ranks (fixed job) instead of the default "
                          "weak scaling (every rank samples its own config-sized read set of the same genome)")
     ap.add_argument("--strong-leg", action="store_true",
-                    help="run the strong-scaled leg at any N (with --sharded at N = 1: rehearses its code path)")
+                    help="--full: run the strong-scaled leg at any N (with --sharded at N = 1: rehearses its code path)")
     ap.add_argument("--no-strong-leg", action="store_true",
-                    help="N > 1 weak-scaled runs: skip the strong-scaled leg (the config's read set split over "
+                    help="--full, N > 1 weak-scaled runs: skip the strong-scaled leg (the config's read set split over "
                          "the ranks, reported under \"strong\")")
     ap.add_argument("--wide-records", action="store_true", help="16-B count records only (EC_FLAG_WIDE_RECORDS)")
     ap.add_argument("--window-records", action="store_true",
@@ -364,7 +409,7 @@ def main():
 
     # timed steps record the kernel events only (EC_FLAG_KERNEL_TIMING: the roofline's kernel
     # durations, live over the timed region); the stage breakdown (EC_FLAG_TIMING, ~26 events
-    # a call, ~0.1 ms) comes from one untimed step after it
+    # a call, ~0.1 ms) comes from one untimed step after it (--full)
     for _ in range(args.warmup):
         step(eulerhip.EC_FLAG_TIMING)
     if use_dist:
@@ -391,8 +436,12 @@ def main():
     # kept between calls, so this is the run's peak allocation)
     hbm_used = hbm_free0 - torch.cuda.mem_get_info()[0]
     timed_phase_ms = dict(runner.phase_ms) if use_dist else None
-    step(eulerhip.EC_FLAG_TIMING)  # untimed (every rank: it has collectives): the per-stage breakdown
-    stage = np.array(list((sess.stats() if not use_dist else runner.stats()).stage_ms))
+    if args.dump_outputs and rank == 0:  # the last timed step's results, still in the session's pinned buffers
+        dump_outputs(args.dump_outputs, (sess if not use_dist else runner.engine.sess).fetch(k))
+    stage = None
+    if args.full:
+        step(eulerhip.EC_FLAG_TIMING)  # untimed (every rank: it has collectives): the per-stage breakdown
+        stage = np.array(list((sess.stats() if not use_dist else runner.stats()).stage_ms))
     st = sess.stats() if not use_dist else runner.stats()
     P = int(st.n_positions) if not use_dist else runner.total_positions
     U = int(st.n_solid) if not use_dist else int(runner.engine.stats().n_solid)
@@ -403,7 +452,7 @@ def main():
     # contiguous shards over the ranks (BASELINE config 4: "10M x 100 bp reads, read-sharded"),
     # timed the same way; reported beside the weak-scaled value
     strong = None
-    if weak and (world > 1 or args.strong_leg) and not args.no_strong_leg:
+    if args.full and weak and (world > 1 or args.strong_leg) and not args.no_strong_leg:
         import distributed
 
         lo, hi = distributed.shard_range(cfg["reads"], rank, world)
@@ -470,15 +519,15 @@ def main():
             "pipeline_alg_bytes": int(alg_bytes(P, R, L, U, K)),
             "pipeline_frac": round(alg_bytes(P, R, L, U, K) / (ms / 1e3) / (HBM_PEAK_GBS * 1e9), 5)}
     host = None
-    if not use_dist and not args.no_host_input:
+    if args.full and not use_dist and not args.no_host_input:
         host = host_input_legs(sess, buf, off, k, P, args.steps, max(2, args.warmup))
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(buf, off, k, args.cpu_sample_reads)
     names = eulerhip.stage_names()
     out = {
         "metric": METRIC, "value": round(value, 1), "unit": "k-mers/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
+        "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "full": args.full,
         "scaling": "none" if world == 1 and not use_dist else ("strong" if args.strong else "weak"),
         "vs_baseline": None, "dtype": "u64" if k <= 32 else "u128",
         "data": "synthetic (iid ACGT genome, uniform %s %d bp reads, 50%% reverse-complemented, numpy PCG64 seed %d)"
@@ -499,7 +548,7 @@ def main():
         "roofline": roof,
         "cpu_baseline": cpu,
         "host_input": host,
-        "stage_ms": {names[i]: round(stage[i], 3) for i in range(len(names))},
+        "stage_ms": {names[i]: round(stage[i], 3) for i in range(len(names))} if stage is not None else None,
         "sharded_phase_ms": sharded_ms,
         "strong": strong,
     }

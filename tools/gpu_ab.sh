@@ -5,7 +5,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 T=$1; shift
-B="bench.py --config ${CFG:-ecoli10m} --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-host-input"
+B="bench.py --full --config ${CFG:-ecoli10m} --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-host-input"
 for rep in 1 2; do
   for v in "$@"; do
     name=${v%%:*}; envs=${v#*:}

@@ -4,7 +4,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 T=$1; shift
-B="bench.py --config ecoli10m_err --steps 10 --warmup 3 --no-cpu-baseline --no-host-input"
+B="bench.py --full --config ecoli10m_err --steps 10 --warmup 3 --no-cpu-baseline --no-host-input"
 i=0
 for arm in "$@"; do
   i=$((i+1))

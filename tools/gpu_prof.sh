@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 TAG=${1:-prof}; CFG=${2:-ecoli10m}
 O=gpurun_out/$TAG; mkdir -p $O
-B="bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-host-input"
+B="bench.py --full --config $CFG --steps 5 --warmup 2 --no-cpu-baseline --no-host-input"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o run -- python3 $B > $O/bench_kt.json 2> $O/kt.err || { echo KT FAILED; tail -20 $O/kt.err; exit 1; }
 cat $O/bench_kt.json
 if [ -z "$NOPMC" ]; then
