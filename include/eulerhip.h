@@ -133,11 +133,15 @@ int ec_session_destroy(ec_session *s);
 int ec_mem_stats(uint64_t *held, uint64_t *peak, int reset);
 /* Release the session's device buffers of at least min_bytes (0: all but its scalars) and every
  * device state they held (dense k-mer arrays, a loaded or placed graph): the next call starts
- * from its inputs; results already copied to host memory stay fetchable.  The sharded path
- * calls it after a large shard's export, so the owner merge and graph phase get the count's
- * memory (distributed.py). */
+ * from its inputs; results already copied to host memory stay fetchable, and batches staged with
+ * ec_stage_packed_host stay staged.  The state is dropped whatever min_bytes released -- also
+ * by a trim that found no buffer that large: records held for an ec_graph_*_copy and emitted
+ * runs are gone after every trim (the copy returns EC_ERR_STATE), the stepwise calls below
+ * return what they return on a new session.  The sharded path calls it after a large shard's
+ * export, so the owner merge and graph phase get the count's memory (distributed.py). */
 int ec_session_trim(ec_session *s, uint64_t min_bytes);
-/* Device bytes the session's buffers hold. */
+/* Device bytes the session's buffers hold (those ec_session_trim can release: the two staged
+ * batches' device copies are not among them). */
 uint64_t ec_session_bytes(ec_session *s);
 
 /* Reads already resident in device memory: d_reads = concatenated ASCII, d_offsets[nreads+1]
@@ -363,6 +367,27 @@ typedef struct {
  * for the same count path); ec_export_by_owner writes global first events. */
 int ec_count_shard(ec_session *s, const uint8_t *d_reads, const uint64_t *d_offsets, uint64_t nreads,
                    uint64_t read_base, int k, unsigned flags);
+/* CALL ORDER of the stepwise calls from here to the end of this header.  A session holds one
+ * piece of device state at a time, and every call that starts from inputs -- ec_assemble_*,
+ * ec_count_shard, ec_merge_owned*, ec_assemble_from_solid / _from_kmers, ec_graph_load* -- and
+ * ec_session_trim (any min_bytes) replace or release it.  A call that needs state which is gone,
+ * or was never made, is refused before it touches the device, ec_last_error says why, and the
+ * session stays usable:
+ *   - ec_export_by_owner* / ec_export_dense need the records of the last ec_count_shard /
+ *     ec_merge_owned*: EC_ERR_STATE after anything else in the list above, after ec_graph_place
+ *     (which moves them) and on a new session;
+ *   - ec_graph_links_part / ec_graph_finish need a set loaded by ec_graph_load that no later
+ *     call replaced (ec_graph_place included: a placed segment has no index): EC_ERR_ARG;
+ *   - ec_graph_join / ec_graph_links_apply need a segment placed by ec_graph_place: EC_ERR_ARG;
+ *   - ec_graph_chains_part needs a loaded set or a placed segment; each later step of the
+ *     partitioned finish needs the one before it on that same set -- chains_part, rank_supers,
+ *     starts_part, layout, then emit_part / emit_runs, collect / collect_runs (layout is enough
+ *     for the collecting calls: the characters arrive as arguments).  A new load / place, a
+ *     join or links_apply (the links changed) and a new chains_part start the sequence over:
+ *     EC_ERR_ARG for a step whose predecessor is missing;
+ *   - the four ec_graph_*_copy calls need the pending records of their step (see "Exact-size
+ *     outputs" below): EC_ERR_STATE when those are gone.
+ * ec_dense_count is 0 after a trim and otherwise the size of whatever the last step held. */
 /* number of dense k-mer records the session holds (after ec_count_shard / ec_merge_owned) */
 uint64_t ec_dense_count(ec_session *s);
 /* pack the held records owner-major into d_out (ec_kmer_record[ec_dense_count]); owner_counts
@@ -482,9 +507,22 @@ int ec_graph_emit_runs(ec_session *s, uint64_t *nbytes);
  * returned as above) and hold them; the matching copy, before any other step of the session,
  * writes them into a buffer of exactly that many records -- instead of the upper bounds (4 Ur
  * junction records, 2 (hi - lo) super / start records: ~50 GB at config 5's per-rank size).
- * ec_graph_chains_part on a placed segment keeps its tile records in the junction-record buffer
- * ec_graph_place filled, so place records still held then are dropped (ec_graph_place_copy
- * returns EC_ERR_STATE). */
+ * The copy delivers the records the same step delivers when given an output buffer: chain and
+ * start records byte for byte, junction records as the same records per owner (their order
+ * inside an owner's group is that of a counting sort with atomic cursors, not fixed).
+ * Pending records live in session buffers (the junction records and, on a placed segment,
+ * ec_graph_chains_part's chain records in the same junction-record buffer), so they are held
+ * only until the session's next step.  One step's records pending, at most; they are dropped by
+ *   - the copy itself (a second copy has nothing to take),
+ *   - ec_session_trim (any min_bytes) and every call that starts from inputs (list above),
+ *   - ec_graph_place (with or without an output: it rewrites the junction-record buffer, chain
+ *     records held there included), ec_graph_join, ec_graph_links_apply,
+ *   - ec_graph_chains_part (place records still held are dropped: it keeps its tile records
+ *     in their buffer), ec_graph_rank_supers, ec_graph_starts_part, ec_graph_layout,
+ * and the late copy returns EC_ERR_STATE without touching the device or its output.  The runs
+ * of ec_graph_emit_runs are held the same way for ec_graph_copy_runs (which may be repeated):
+ * dropped by all of the above and by ec_graph_collect_runs, which reuses their buffer;
+ * ec_graph_copy_runs then returns EC_ERR_STATE (EC_ERR_ARG is a NULL argument). */
 int ec_graph_place_copy(ec_session *s, void *d_jrecs);
 int ec_graph_chains_copy(ec_session *s, void *d_super);
 int ec_graph_starts_copy(ec_session *s, void *d_starts);

@@ -239,6 +239,7 @@ struct ec_session {
     bool timing = false;        // kernel events (EC_FLAG_TIMING or EC_FLAG_KERNEL_TIMING)
     bool stage_timing = false;  // stage events (EC_FLAG_TIMING)
     unsigned int n_dense = 0;  // dense k-mer arrays held by the session (shard / merge steps)
+    bool dense_ok = false;     // ... as ec_count_shard / ec_merge_owned left them (ec_export_* valid)
     bool stats_ok = false;     // ec_get_stats valid (any successful call)
     unsigned flags = 0;        // flags of the current call
     DevBuf ocnt, rbc, mbid, mbid2, midx, midx2, gcur, cwalk, ewalk, lc8;
@@ -346,7 +347,21 @@ struct ec_session {
     unsigned long long lb_epoch = 0;
     uint64_t run_nr = 0, run_nch = 0, run_nends = 0;
     bool runs_ready = false;
+    // how far the partitioned finish of the loaded / placed set has come: each step needs the one
+    // before it (0 none, 1 chains, 2 super ranking, 3 starts, 4 layout, 5 emitted)
+    int part_stage = 0;
 };
+
+// Every piece of step state that points into session buffers: records held for an ec_graph_*_copy,
+// the emitted runs, the chain records' scratch, the partitioned finish's progress.  Dropped by
+// whatever releases, rewrites or may reallocate those buffers (trim, a new call, a new load /
+// place / join), so a late copy or step is refused instead of reading them (include/eulerhip.h).
+static inline void drop_step_state(ec_session *s) {
+    s->hold.kind = 0;
+    s->runs_ready = false;
+    s->chain_scr = nullptr;
+    s->part_stage = 0;
+}
 
 namespace {
 constexpr size_t BOUNCE_CAP = 64 << 10, BOUNCE_MAX = 16 << 10;  // bytes; larger reads go direct
@@ -537,7 +552,9 @@ void collect_timing(ec_session *s) {
 // zeroed device scalars
 int begin_call(ec_session *s, int k, unsigned flags) {
     s->xalpha = false;  // (set by the extended-alphabet path, extended.h)
-    s->hold.kind = 0;
+    drop_step_state(s);
+    s->graph_loaded = false;  // (the call rewrites the buffers a loaded / placed graph lives in)
+    s->dense_ok = false;
     refresh_knobs();
     s->have = false;
     s->stats_ok = false;
@@ -3370,6 +3387,10 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
 //   ec_graph_collect      rank 0: the summed characters / ends -> GFA links and the results
 // the chain records of k_tile_chains compacted into d_super (M of them)
 int part_chains_copy(ec_session *s, uint64_t M, unsigned int ntiles, bool planned, SuperRec *d_super) {
+    if (!s->chain_scr) {  // (the tile records' buffer was released or rewritten since ec_graph_chains_part)
+        set_error("ec_graph_chains_copy: the chain records are gone");
+        return EC_ERR_STATE;
+    }
     hipStream_t st = s->stream;
     if (M)
         k_tile_compact<<<ntiles, 256, 0, st>>>(s->chain_scr, s->rt_tcnt.as<unsigned long long>(),
@@ -3389,6 +3410,9 @@ int part_chains(ec_session *s, uint64_t lo, uint64_t hi, const uint32_t *d_succ,
     const unsigned int U = (unsigned int)s->n_dense, N = 2 * U;
     const size_t Nn = std::max<size_t>(N, 1);
     const unsigned int n0 = (unsigned int)(2 * lo), n1 = (unsigned int)(2 * hi);
+    // (the chains are ranked anew: held records, emitted runs and later steps of an earlier
+    // ranking are stale -- their buffers are rewritten below)
+    drop_step_state(s);
     EC_CHECK(s->upal.ensure(std::max<size_t>(U, 1)));
     EC_CHECK(s->succ.ensure(Nn * 4));
     EC_CHECK(s->PK.ensure(Nn * 4));
@@ -3426,7 +3450,6 @@ int part_chains(ec_session *s, uint64_t lo, uint64_t hi, const uint32_t *d_succ,
     const size_t scr_bytes =
         std::max<size_t>(planned ? 2 * (size_t)(hi - lo) : (size_t)ntiles * RT_TN, 1) * sizeof(SuperRec);
     DevBuf &scr = s->placed && s->jrec.cap >= scr_bytes ? s->jrec : s->st1;
-    if (&scr == &s->jrec && s->hold.kind == 1) s->hold.kind = 0;
     EC_CHECK(scr.ensure(scr_bytes));
     unsigned long long *tcnt = s->rt_tcnt.as<unsigned long long>(), *tbase = s->rt_tbase.as<unsigned long long>();
     SuperRec *scratch = reinterpret_cast<SuperRec *>(scr.p);
@@ -3445,6 +3468,7 @@ int part_chains(ec_session *s, uint64_t lo, uint64_t hi, const uint32_t *d_succ,
     *n_super = M;
     s->seg_n0 = n0;
     s->seg_n1 = n1;
+    s->part_stage = 1;
     if (!d_super) {  // counted only: ec_graph_chains_copy compacts them
         s->hold = ec_session::Pending{2, M, ntiles, planned};
         return EC_OK;
@@ -3455,10 +3479,16 @@ int part_chains(ec_session *s, uint64_t lo, uint64_t hi, const uint32_t *d_succ,
 int part_rank(ec_session *s, const SuperRec *d_all, uint64_t M) {
     hipStream_t st = s->stream;
     s->hold.kind = 0;  // (the next steps reuse the held records' buffers)
+    s->chain_scr = nullptr;
+    s->runs_ready = false;
+    s->part_stage = 1;  // (2 once the ranking is done)
     Scalars *dsc = s->scal.as<Scalars>();
     const unsigned int N = 2 * (unsigned int)s->n_dense;
     s->stats.n_rulers = 0;
-    if (!M) return EC_OK;
+    if (!M) {
+        s->part_stage = 2;
+        return EC_OK;
+    }
     // the super list's buffers sized by its chain count (1/16 spare on first allocation, so a
     // step whose count is a little above the last one's reuses them), not by the node count:
     // config 5's one-rank step ranks 21 M chains of 400 M nodes, where node-sized ruler state
@@ -3491,6 +3521,7 @@ int part_rank(ec_session *s, const SuperRec *d_all, uint64_t M) {
         if (hsc.nvisited == M && hsc.active[rounds - 1] == 0) {
             s->stats.n_rulers = hsc.nr;
             s->stats.rank_rounds = rounds_used(hsc, rounds);
+            s->part_stage = 2;
             return EC_OK;
         }
         if (kn().verbose)
@@ -3507,6 +3538,7 @@ int part_rank(ec_session *s, const SuperRec *d_all, uint64_t M) {
         return EC_ERR_STATE;
     }
     s->stats.rank_rounds = rounds;
+    s->part_stage = 2;
     return EC_OK;
 }
 
@@ -3529,7 +3561,13 @@ int part_starts(ec_session *s, bool have_supers, StartRec *d_starts, uint64_t *n
     const unsigned int n0 = (unsigned int)s->seg_n0, n1 = (unsigned int)s->seg_n1;
     const size_t Nn = std::max<size_t>(2 * (size_t)s->n_dense, 1);
     *n_starts = 0;
-    if (n1 <= n0) return EC_OK;
+    s->hold.kind = 0;
+    s->runs_ready = false;
+    s->part_stage = 2;  // (3 once the starts are listed)
+    if (n1 <= n0) {
+        s->part_stage = 3;
+        return EC_OK;
+    }
     if (have_supers)
         k_expand<<<grid_for(n1 - n0, B), B, 0, st>>>(s->pred.as<unsigned int>(), s->rt_lr.as<unsigned int>(), n1,
                                                      s->rt_sidx.as<unsigned int>(), s->rt_pks.as<unsigned int>(),
@@ -3554,6 +3592,7 @@ int part_starts(ec_session *s, bool have_supers, StartRec *d_starts, uint64_t *n
     EC_CHECK(d2h(s, &cnt, bs + nblk - 1, 4, st));
     EC_CHECK(host_sync(s, st));
     *n_starts = cnt;
+    s->part_stage = 3;
     if (!d_starts) {  // counted only: ec_graph_starts_copy writes them
         s->hold = ec_session::Pending{3, cnt, 0, false};
         return EC_OK;
@@ -3564,6 +3603,8 @@ int part_starts(ec_session *s, bool have_supers, StartRec *d_starts, uint64_t *n
 int part_layout(ec_session *s, const StartRec *d_all, uint64_t nc, uint64_t *n_chars) {
     hipStream_t st = s->stream;
     s->hold.kind = 0;
+    s->runs_ready = false;  // (runs emitted under an earlier layout: their chunk counts do not fit this one)
+    s->part_stage = 3;      // (4 once the layout stands)
     const unsigned B = 256;
     const size_t Nn = std::max<size_t>(2 * (size_t)s->n_dense, 1), nn = std::max<size_t>(nc, 1);
     EC_CHECK(s->skeys.ensure(nn * 8));
@@ -3592,6 +3633,7 @@ int part_layout(ec_session *s, const StartRec *d_all, uint64_t nc, uint64_t *n_c
     s->seg_nc = (unsigned int)nc;
     s->seg_nchars = tot;
     *n_chars = tot;
+    s->part_stage = 4;
     return EC_OK;
 }
 
@@ -3634,6 +3676,7 @@ int part_emit(ec_session *s, char *d_chars, void *d_ends, bool check = true) {
         set_error("contig characters past their bound %llu (inconsistent ranking)", (unsigned long long)s->seg_nchars);
         return EC_ERR_STATE;
     }
+    s->part_stage = 5;
     return EC_OK;
 }
 
@@ -3756,6 +3799,7 @@ int part_emit_runs(ec_session *s, uint64_t *nbytes) {
     s->run_nch = tot[1];
     s->run_nends = ne;
     s->runs_ready = true;
+    s->part_stage = 5;
     *nbytes = run_rec_bytes(tot[0], tot[1], ne, (int)sizeof(K));
     return EC_OK;
 }
@@ -3799,6 +3843,7 @@ int part_collect_runs(ec_session *s, const uint8_t *d_in, int nsrc, const uint64
         o += src_bytes[r];
     }
     EC_CHECK(host_sync(s, st));
+    s->runs_ready = false;  // (the job's characters go where this rank's emitted runs were)
     EC_CHECK(s->chars.ensure(nchars + 32));
     EC_CHECK(s->run_dends.ensure(std::max<size_t>(2ull * nc, 1) * sizeof(K)));
     EC_HIP(hipMemsetAsync(s->run_dends.p, 0, std::max<size_t>(2ull * nc, 1) * sizeof(K), st));
@@ -4237,7 +4282,10 @@ int ec_session_trim(ec_session *s, uint64_t min_bytes) {
     });
     // no device state survives: the next call starts from its inputs (results already copied to
     // host memory stay fetchable)
+    // (whatever min_bytes released: a trim always drops the held records and emitted runs too)
+    drop_step_state(s);
     s->n_dense = 0;
+    s->dense_ok = false;
     s->own_valid = false;
     s->bmark_ok = false;
     s->seg_marks = 0;
@@ -4550,6 +4598,7 @@ int ec_count_shard(ec_session *s, const uint8_t *d_reads, const uint64_t *d_offs
     EC_CHECK(rc);
     s->shard_base = read_base;
     s->n_dense = U;
+    s->dense_ok = true;
     collect_timing(s);
     s->stats_ok = true;
     return EC_OK;
@@ -4575,6 +4624,10 @@ int ec_export_by_owner_ex(ec_session *s, int nowners, void *d_out, uint64_t *own
     if (!s || nowners < 1 || nowners > MAX_OWNERS || !owner_counts) {
         set_error("bad ec_export_by_owner arguments (nowners=%d)", nowners);
         return EC_ERR_ARG;
+    }
+    if (!s->dense_ok) {
+        set_error("ec_export_by_owner: no counted or merged records (ec_count_shard / ec_merge_owned)");
+        return EC_ERR_STATE;
     }
     EC_HIP(hipSetDevice(s->device));
     hipStream_t st = s->stream;
@@ -4676,6 +4729,7 @@ int merge_owned_impl(ec_session *s, const void *d_records, uint64_t n, int k, in
     s->no_index = false;
     EC_CHECK(rc);
     s->n_dense = U;
+    s->dense_ok = true;
     collect_timing(s);
     s->stats_ok = true;
     return EC_OK;
@@ -4763,6 +4817,10 @@ int ec_compact_record_bytes(int k) { return k > 32 ? (int)sizeof(CRecW) : (int)s
 
 int ec_export_dense(ec_session *s, void *d_out) {
     if (!s) return EC_ERR_ARG;
+    if (!s->dense_ok) {
+        set_error("ec_export_dense: no counted or merged records (ec_count_shard / ec_merge_owned)");
+        return EC_ERR_STATE;
+    }
     EC_HIP(hipSetDevice(s->device));
     const unsigned int n = s->n_dense;
     if (n && d_out) {
@@ -4837,7 +4895,7 @@ int ec_graph_load(ec_session *s, const void *d_records, uint64_t n, int k, unsig
 
 int ec_graph_links_part(ec_session *s, uint64_t lo, uint64_t hi, uint32_t *d_succ) {
     refresh_knobs();
-    if (!s || !s->graph_loaded || lo > hi || hi > s->n_dense || (hi > lo && !d_succ)) {
+    if (!s || !s->graph_loaded || s->placed || lo > hi || hi > s->n_dense || (hi > lo && !d_succ)) {
         set_error("ec_graph_links_part: no loaded solid set or bad range [%llu, %llu)", (unsigned long long)lo,
                   (unsigned long long)hi);
         return EC_ERR_ARG;
@@ -4897,8 +4955,8 @@ int ec_graph_chains_part(ec_session *s, uint64_t lo, uint64_t hi, const uint32_t
 }
 
 int ec_graph_rank_supers(ec_session *s, const void *d_supers, uint64_t n) {
-    if (!s || !s->graph_loaded || (n && !d_supers)) {
-        set_error("ec_graph_rank_supers: no loaded solid set");
+    if (!s || !s->graph_loaded || s->part_stage < 1 || (n && !d_supers)) {
+        set_error("ec_graph_rank_supers: no loaded solid set with ranked chains (ec_graph_chains_part)");
         return EC_ERR_ARG;
     }
     EC_HIP(hipSetDevice(s->device));
@@ -4906,8 +4964,8 @@ int ec_graph_rank_supers(ec_session *s, const void *d_supers, uint64_t n) {
 }
 
 int ec_graph_starts_part(ec_session *s, int have_supers, void *d_starts, uint64_t *n_starts) {
-    if (!s || !s->graph_loaded || !n_starts) {
-        set_error("ec_graph_starts_part: no loaded solid set");
+    if (!s || !s->graph_loaded || s->part_stage < 2 || !n_starts) {
+        set_error("ec_graph_starts_part: no loaded solid set with ranked supers (ec_graph_rank_supers)");
         return EC_ERR_ARG;
     }
     EC_HIP(hipSetDevice(s->device));
@@ -4941,6 +4999,7 @@ int ec_graph_place_copy(ec_session *s, void *d_jrecs) {
 
 int ec_graph_chains_copy(ec_session *s, void *d_super) {
     uint64_t n = 0;
+    if (s && s->hold.kind == 2 && !s->chain_scr) s->hold.kind = 0;  // (records gone: refused below)
     EC_CHECK(take_pending(s, 2, d_super, "ec_graph_chains_copy", n));
     return part_chains_copy(s, n, s->hold.ntiles, s->hold.planned, static_cast<SuperRec *>(d_super));
 }
@@ -4952,8 +5011,8 @@ int ec_graph_starts_copy(ec_session *s, void *d_starts) {
 }
 
 int ec_graph_layout(ec_session *s, const void *d_starts, uint64_t n, uint64_t *n_chars) {
-    if (!s || !s->graph_loaded || !n_chars || (n && !d_starts)) {
-        set_error("ec_graph_layout: no loaded solid set");
+    if (!s || !s->graph_loaded || s->part_stage < 3 || !n_chars || (n && !d_starts)) {
+        set_error("ec_graph_layout: no loaded solid set with its starts (ec_graph_starts_part)");
         return EC_ERR_ARG;
     }
     EC_HIP(hipSetDevice(s->device));
@@ -4961,7 +5020,7 @@ int ec_graph_layout(ec_session *s, const void *d_starts, uint64_t n, uint64_t *n
 }
 
 int ec_graph_emit_part(ec_session *s, char *d_chars, void *d_ends) {
-    if (!s || !s->graph_loaded || (s->seg_nchars && !d_chars) || (s->seg_nc && !d_ends)) {
+    if (!s || !s->graph_loaded || s->part_stage < 4 || (s->seg_nchars && !d_chars) || (s->seg_nc && !d_ends)) {
         set_error("ec_graph_emit_part: no layout");
         return EC_ERR_ARG;
     }
@@ -4970,7 +5029,8 @@ int ec_graph_emit_part(ec_session *s, char *d_chars, void *d_ends) {
 }
 
 int ec_graph_collect(ec_session *s, const char *d_chars, const void *d_ends, uint64_t n_pal) {
-    if (!s || !s->graph_loaded || (s->seg_nchars && !d_chars) || (s->seg_nc && !d_ends) || 2 * n_pal > 2 * s->n_dense) {
+    if (!s || !s->graph_loaded || s->part_stage < 4 || (s->seg_nchars && !d_chars) || (s->seg_nc && !d_ends) ||
+        2 * n_pal > 2 * s->n_dense) {
         set_error("ec_graph_collect: no layout");
         return EC_ERR_ARG;
     }
@@ -4979,7 +5039,7 @@ int ec_graph_collect(ec_session *s, const char *d_chars, const void *d_ends, uin
 }
 
 int ec_graph_emit_runs(ec_session *s, uint64_t *nbytes) {
-    if (!s || !s->graph_loaded || !nbytes) {
+    if (!s || !s->graph_loaded || s->part_stage < 4 || !nbytes) {
         set_error("ec_graph_emit_runs: no layout");
         return EC_ERR_ARG;
     }
@@ -4988,16 +5048,20 @@ int ec_graph_emit_runs(ec_session *s, uint64_t *nbytes) {
 }
 
 int ec_graph_copy_runs(ec_session *s, void *d_out) {
-    if (!s || !s->runs_ready || !d_out) {
-        set_error("ec_graph_copy_runs: no emitted runs (ec_graph_emit_runs)");
+    if (!s || !d_out) {
+        set_error("ec_graph_copy_runs: null argument");
         return EC_ERR_ARG;
+    }
+    if (!s->runs_ready || !s->graph_loaded) {
+        set_error("ec_graph_copy_runs: no emitted runs (ec_graph_emit_runs)");
+        return EC_ERR_STATE;
     }
     EC_HIP(hipSetDevice(s->device));
     return s->k > 32 ? part_copy_runs<OpsW>(s, d_out) : part_copy_runs<Ops64>(s, d_out);
 }
 
 int ec_graph_collect_runs(ec_session *s, const void *d_in, int nsrc, const uint64_t *src_bytes, uint64_t n_pal) {
-    if (!s || !s->graph_loaded || nsrc < 1 || !src_bytes || !d_in || n_pal > s->n_dense) {
+    if (!s || !s->graph_loaded || s->part_stage < 4 || nsrc < 1 || !src_bytes || !d_in || n_pal > s->n_dense) {
         set_error("ec_graph_collect_runs: no layout or bad arguments");
         return EC_ERR_ARG;
     }
@@ -5032,6 +5096,12 @@ int graph_place(ec_session *s, uint64_t lo, uint64_t U, int nowners, void *d_out
     const unsigned B = 256;
     Scalars *dsc = s->scal.as<Scalars>();
     const uint64_t Ur = s->n_dense, Uu = std::max<uint64_t>(U, 1);
+    // (the dense arrays, the successors and the junction records -- a chains step's records among
+    // them -- are rewritten: nothing held or ranked on them survives; loaded / placed again at the end)
+    drop_step_state(s);
+    s->graph_loaded = false;
+    s->placed = false;
+    s->dense_ok = false;
     // the merge's dense arrays [0, Ur) -> global ids [lo, lo + Ur) of U-sized arrays
     EC_CHECK(s->recs.ensure(std::max<uint64_t>(Ur, 1) * sizeof(K)));
     EC_CHECK(s->recs2.ensure(std::max<uint64_t>(Ur, 1) * 16));
@@ -5124,7 +5194,7 @@ int graph_join(ec_session *s, const R *d_recs, uint64_t n, int nowners, const ui
                uint64_t *owner_counts) {
     hipStream_t st = s->stream;
     const unsigned B = 256;
-    s->hold.kind = 0;
+    drop_step_state(s);  // (held place records' index, and chains ranked on the links this join rewrites)
     constexpr int BT_CS = 14, BT_MAX = 22;  // counting sort's LDS histogram limit; radix sort past it
     EC_CHECK(s->jseg.ensure(((size_t)nowners + 2) * 8 + ((size_t)(1u << BT_MAX) + 1) * 8 + 64));
     unsigned long long *dseg = s->jseg.as<unsigned long long>();
@@ -5260,6 +5330,7 @@ int ec_graph_links_apply(ec_session *s, const void *d_links, uint64_t n) {
         set_error("ec_graph_links_apply: no placed segment");
         return EC_ERR_ARG;
     }
+    drop_step_state(s);  // (the links change: chains ranked on them are stale)
     EC_HIP(hipSetDevice(s->device));
     hipStream_t st = s->stream;
     EC_CHECK(s->jcnt.ensure(16));
