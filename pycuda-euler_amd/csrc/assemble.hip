@@ -907,6 +907,9 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
     EC_CHECK(s->dfc.ensure(umax * 8));
     EC_CHECK(s->dft.ensure(umax * 8));
     EC_CHECK(s->sub.ensure(umax * sizeof(SubSlot)));
+    bool b3_marked = false;
+    // (run twice when a final bucket outgrew fcap and the capacity the refine measured is in reach)
+    for (int attempt = 0;; attempt++) {
     kmark(s, 2, 0);
     const double inv_m = 1.0 / M;
     // records deduplicated per bucket before their windows are rolled out (k_skbucket3 /
@@ -918,7 +921,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
 #define EC_SKBUCKET(SLOTS, RS, EVEN) \
     k_skbucket<SLOTS, RS, 1, EVEN><<<(unsigned)Bk, BUCKET_THREADS, 0, st>>>(EC_SKBUCKET_ARGS, dbg)
     // EULERHIP_SK2_STATS: distinct records, flushes and windows rolled out (stderr)
-    bool b3_marked = false;
+    b3_marked = false;
     unsigned long long *dbg = nullptr;
     if (kn().sk2_stats) {
         EC_CHECK(s->tmp.ensure(128));
@@ -1021,6 +1024,27 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
     mark(s, 2 * EC_STAGE_COMPACT + 1);
     EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
     EC_CHECK(host_sync(s, st));
+    if (!hsc.skew || attempt) break;
+    // a final bucket past fcap: a repeat family's minimizers (copies x coverage records each) on an
+    // input whose buckets hold a few thousand records.  k_skrefine's cursors counted every record,
+    // so the fullest bucket's need is known: refined and counted once more with that capacity
+    // while it stays within 4x the plan's and 1 GiB of records, instead of leaving the super-k-mer
+    // path for the whole call (extreme skew still does, below)
+    std::vector<unsigned long long> hcur(Bk);
+    EC_CHECK(d2h(s, hcur.data(), s->fcur.p, Bk * 8, st));
+    EC_CHECK(host_sync(s, st));
+    const uint64_t need = *std::max_element(hcur.begin(), hcur.end());
+    if (need <= fcap || need > 4 * fcap || Bk * need * 16 > (1ull << 30)) break;
+    if (verbose)
+        fprintf(stderr, "count_sk2: final bucket overflow (fcap %llu), refined again with capacity %llu\n",
+                (unsigned long long)fcap, (unsigned long long)need);
+    fcap = need;  // (the speculative plan keeps the planned capacity: the next call measures its own)
+    EC_HIP(hipMemsetAsync(&dsc->overflow, 0, sizeof(unsigned int), st));
+    EC_HIP(hipMemsetAsync(&dsc->skew, 0, sizeof(unsigned int), st));
+    EC_HIP(hipMemsetAsync(&dsc->nsolid, 0, sizeof(unsigned int), st));
+    EC_HIP(hipMemsetAsync(&dsc->ndistinct, 0, sizeof(unsigned long long), st));
+    EC_CHECK(launch_refine(bbits, fcap));
+    }
     if (hsc.overflow || hsc.skew) {  // a final bucket or an LDS table overflowed
         if (verbose)
             fprintf(stderr, "count_sk2: %s overflow (%llu buckets, %u slots, est %.0f, fcap %llu)\n",
@@ -3564,8 +3588,9 @@ int part_starts(ec_session *s, bool have_supers, StartRec *d_starts, uint64_t *n
     s->hold.kind = 0;
     s->runs_ready = false;
     s->part_stage = 2;  // (3 once the starts are listed)
-    if (n1 <= n0) {
+    if (n1 <= n0) {  // an empty segment (a rank that owns no solid key): no starts, counted as such
         s->part_stage = 3;
+        if (!d_starts) s->hold = ec_session::Pending{3, 0, 0, false};
         return EC_OK;
     }
     if (have_supers)
