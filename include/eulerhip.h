@@ -63,8 +63,10 @@ typedef struct ec_session ec_session;
 #define EC_FLAG_EXACT_COUNT 64u /* partitioned path: histogram-sized runs only (count_part.h), never the
                                   * fixed-capacity runs of count_v2.h */
 #define EC_FLAG_SUPERKMER 32u /* accepted and ignored: super-k-mer records (count_sk2.h, ec_stats.count_variant 3)
-                                * are the default where they apply -- N-free reads of one length,
-                                * 21 <= k <= 32; the 32-B record path this flag selected was removed */
+                                * are the default where they apply -- N-free reads whose reads of k or more
+                                * bases are all of one length (shorter reads, which have no window, may stand
+                                * beside them), 21 <= k <= 32; the 32-B record path this flag selected was
+                                * removed */
 
 #define EC_NSTAGES 8
 /* stage ids for ec_stats.stage_ms / ec_stage_name */
@@ -113,8 +115,9 @@ typedef struct {
                               * 1 = fixed-capacity runs without the upsweep (count_v2.h), 12-B
                               * records; 2 = the same with 10-B records (hashed-key remnants);
                               * 3 = 16-B super-k-mer records on fixed-capacity runs
-                              * (count_sk2.h; the default for N-free reads of one length,
-                              * 21 <= k <= 32, inputs that need no seen-twice filter)          */
+                              * (count_sk2.h; the default for N-free reads of one length -- not
+                              * counting reads shorter than k -- 21 <= k <= 32, inputs that need
+                              * no seen-twice filter)                                         */
     float stage_ms[EC_NSTAGES];   /* EC_FLAG_TIMING only */
     float kernel_ms[EC_NKERNELS]; /* EC_FLAG_TIMING or EC_FLAG_KERNEL_TIMING */
 } ec_stats;

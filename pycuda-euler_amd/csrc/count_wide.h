@@ -248,6 +248,7 @@ __global__ void __launch_bounds__(TILE_READS) k_upsweep_w(const uint8_t *buf, co
             continue;
         }
         if (len < (uint64_t)k) continue;
+        if (MB && len - k + 1 != (uint64_t)mbM) continue;  // (no minimizers for it: as k_upsweep_runs)
         const uint32_t m = (uint32_t)(len - k + 1);
         mypos += m;
         mymax = max(mymax, 2 * m - 1);
@@ -337,6 +338,9 @@ __global__ void __launch_bounds__(TILE_READS) k_upsweep_runs(const uint8_t *buf,
         const uint64_t s = off[r];
         const uint64_t len = off[r + 1] - s;
         if (len < (uint64_t)k) continue;
+        // a read of another length has no minimizers (k_wbv raised *bad for it; the host redoes the
+        // call on hash buckets): a longer one's windows would be read past its mbM rows of wbv
+        if (len - k + 1 != (uint64_t)mbM) continue;
         const uint32_t m = (uint32_t)(len - k + 1);
         mypos += m;
         mymax = max(mymax, 2 * m - 1);
