@@ -196,6 +196,40 @@ int ec_copy_links(ec_session *s, uint64_t *link_offsets, int64_t *links);
 /* ordered dict of build(): kmers[n_dict*k] chars, counts[n_dict]; needs EC_FLAG_WANT_DICT */
 int ec_copy_dict(ec_session *s, char *kmers, uint32_t *counts);
 
+/* Tip clipping on the session's results (csrc/clip.h) -- graph clean-up that goes beyond the
+ * reference, whose all_contigs stops at the raw unitig graph.  With (G, r) the session's current
+ * all_contigs result, len_i = len(r[i]) and max_tip_len in characters (0: 2 k):
+ *   - contig i is a candidate iff len_i <= max_tip_len and exactly one of G[i][0], G[i][1] is
+ *     empty (a = its non-empty side); isolated contigs and contigs linked on both sides never are;
+ *   - its siblings: per link (j, o) of G[i][a] the entries (i2, _) of G[j][t], i2 != i, with
+ *     t = 1 if o == '+' (the link enters j at its head) else 0;
+ *   - it is clipped iff some sibling is no candidate, or len_i2 > len_i, or len_i2 == len_i and
+ *     i2 < i (of two equal tips at a fork one survives; a short stem that forks is no tip);
+ *   - clipping removes every k-mer window of r[i], and its twin, from the dict; the order (first
+ *     events) of the remaining entries is unchanged.
+ * Up to max_rounds times: evaluate the rule; no contig clipped -> converged = 1, stop; else remove
+ * the k-mers, run the graph phase on the remaining set, rounds += 1.  A run that uses max_rounds
+ * up ends with converged = 0.  The session always holds the results of the current dict:
+ * ec_copy_contigs / ec_copy_links deliver the clipped graph, ec_copy_dict the clipped dict (if the
+ * assembly had EC_FLAG_WANT_DICT), ec_get_stats its n_solid, n_dict, n_contigs, n_contig_chars,
+ * n_links (n_rulers, rank_rounds: the last graph phase's) beside the assembly's counting fields
+ * (n_reads, n_positions, n_distinct*, count_path, count_variant, n_buckets, record_bytes,
+ * n_records, table_*); timing fields are unspecified.  A call whose first evaluation finds no tip
+ * leaves every result byte as it was (rounds = 0, converged = 1).
+ * Valid after a successful ec_assemble_device / _host / _packed_host / _staged / _packed_reads,
+ * ec_assemble_from_solid, ec_assemble_from_kmers or ec_clip_tips, on standard-alphabet results.
+ * Refused before touching the device (the session stays usable, earlier results fetchable):
+ * EC_ERR_ARG for a NULL session or info or max_rounds = 0; EC_ERR_STATE, ec_last_error naming the
+ * case, on a new session, after ec_session_trim, after the stepwise calls (ec_count_shard,
+ * ec_merge_owned*, ec_graph_*), after a failed call and on extended-alphabet results. */
+typedef struct {
+    uint32_t rounds;        /* rounds that clipped >= 1 contig (= graph phases re-run)   */
+    uint32_t converged;     /* 1: the last evaluation found no tip                      */
+    uint64_t n_tip_contigs; /* contigs clipped, all rounds                              */
+    uint64_t n_tip_kmers;   /* canonical k-mers removed, all rounds                     */
+} ec_clip_info;
+int ec_clip_tips(ec_session *s, uint32_t max_tip_len, uint32_t max_rounds, ec_clip_info *info);
+
 /* ---- layer 2: per-module drop-ins (host buffers, one H2D/D2H round trip per call) ---------
  * Each restates the INTENDED semantics of the reference PyCUDA function named; the reference's
  * out-of-bounds and race defects are fixed, flags reproduce them where a caller may
@@ -372,7 +406,8 @@ int ec_count_shard(ec_session *s, const uint8_t *d_reads, const uint64_t *d_offs
                    uint64_t read_base, int k, unsigned flags);
 /* CALL ORDER of the stepwise calls from here to the end of this header.  A session holds one
  * piece of device state at a time, and every call that starts from inputs -- ec_assemble_*,
- * ec_count_shard, ec_merge_owned*, ec_assemble_from_solid / _from_kmers, ec_graph_load* -- and
+ * ec_count_shard, ec_merge_owned*, ec_assemble_from_solid / _from_kmers, ec_graph_load*,
+ * ec_clip_tips (its own inputs are the results of the assembly before it) -- and
  * ec_session_trim (any min_bytes) replace or release it.  A call that needs state which is gone,
  * or was never made, is refused before it touches the device, ec_last_error says why, and the
  * session stays usable:

@@ -44,6 +44,7 @@
 #include "rank_tile.h"
 #include "junction.h"
 #include "join_local.h"
+#include "clip.h"
 
 #include <atomic>
 #include <chrono>
@@ -350,7 +351,21 @@ struct ec_session {
     // how far the partitioned finish of the loaded / placed set has come: each step needs the one
     // before it (0 none, 1 chains, 2 super ranking, 3 starts, 4 layout, 5 emitted)
     int part_stage = 0;
+    // ec_clip_tips (clip.h): valid only on the results of a one-GPU graph phase whose dense arrays,
+    // lookup index, contig characters / offsets and link table are still on the device.  clip_ok is
+    // set where such a phase ends and cleared by everything that rewrites or releases them
+    // (begin_call, trim); clip_why says what the refusal reports.  cidx / cidxw: the index the
+    // count or merge returned, kept past the call (as gidx / gidxw keep a loaded set's)
+    bool clip_ok = false;
+    const char *clip_why = "a new session holds no assembly";
+    SolidIndex cidx{};
+    SolidIndexW cidxw{};
+    DevBuf clip_cand, clip_list, clip_kill, clip_tot;
 };
+
+// ec_clip_tips' refusal after the stepwise calls (ec_session::clip_why)
+static const char *const CLIP_WHY_STEPWISE =
+    "the last calls were stepwise ones (ec_count_shard / ec_merge_owned* / ec_graph_*), which leave no one-GPU assembly";
 
 // Every piece of step state that points into session buffers: records held for an ec_graph_*_copy,
 // the emitted runs, the chain records' scratch, the partitioned finish's progress.  Dropped by
@@ -555,6 +570,8 @@ int begin_call(ec_session *s, int k, unsigned flags) {
     drop_step_state(s);
     s->graph_loaded = false;  // (the call rewrites the buffers a loaded / placed graph lives in)
     s->dense_ok = false;
+    s->clip_ok = false;  // (... and the dense arrays, index and results ec_clip_tips reads)
+    s->clip_why = "the session's last call failed";
     refresh_knobs();
     s->have = false;
     s->stats_ok = false;
@@ -2852,6 +2869,10 @@ inline bool ids_minimizer_local<SolidIndex>(const SolidIndex &x) { return x.sk !
 template <>
 inline bool ids_minimizer_local<SolidIndexW>(const SolidIndexW &x) { return x.mb != 0; }
 
+// the index of the set a one-GPU graph phase ran on, kept for ec_clip_tips' window lookups
+inline void keep_index(ec_session *s, const SolidIndex &x) { s->cidx = x; }
+inline void keep_index(ec_session *s, const SolidIndexW &x) { s->cidxw = x; }
+
 // all_contigs:79-111 on the device from the solid set of phase_count / phase_merge
 template <typename Ops, typename Index>
 int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const unsigned int *ext_succ = nullptr) {
@@ -3398,6 +3419,14 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
     collect_timing(s);
     s->have = true;
     s->stats_ok = true;
+    // ec_clip_tips works on what this phase leaves: the dense arrays with the index k_gfa just
+    // read, chars / coff, lk / lcnt -- of a complete set (no partitioned links) on A/C/G/T
+    if (XT) s->clip_why = "the results are on an extended alphabet";
+    else if (ext_succ) s->clip_why = CLIP_WHY_STEPWISE;
+    else {
+        keep_index(s, sidx);
+        s->clip_ok = true;
+    }
     return EC_OK;
 }
 
@@ -4240,7 +4269,8 @@ static void for_each_buf(ec_session *s, Fn fn) {
                      &s->jrec, &s->joid, &s->jout, &s->jseg, &s->jcnt, &s->xrec,
                      &s->skm_rec, &s->skm_ev, &s->skm_end, &s->wcodes_tab,
                      &s->run_cnt, &s->run_ends, &s->run_dends, &s->rt_lb,
-                     &s->jl_kof, &s->jl_rs, &s->jl_re, &s->jl_cnt, &s->jl_off, &s->jl_flag, &s->rpack};
+                     &s->jl_kof, &s->jl_rs, &s->jl_re, &s->jl_cnt, &s->jl_off, &s->jl_flag, &s->rpack,
+                     &s->clip_cand, &s->clip_list, &s->clip_kill, &s->clip_tot};
     for (auto *b : all) fn(*b);
 }
 
@@ -4311,6 +4341,8 @@ int ec_session_trim(ec_session *s, uint64_t min_bytes) {
     drop_step_state(s);
     s->n_dense = 0;
     s->dense_ok = false;
+    s->clip_ok = false;
+    s->clip_why = "ec_session_trim released the assembly's device state";
     s->own_valid = false;
     s->bmark_ok = false;
     s->seg_marks = 0;
@@ -4621,6 +4653,7 @@ int ec_count_shard(ec_session *s, const uint8_t *d_reads, const uint64_t *d_offs
     }
     s->no_index = false;
     EC_CHECK(rc);
+    s->clip_why = CLIP_WHY_STEPWISE;
     s->shard_base = read_base;
     s->n_dense = U;
     s->dense_ok = true;
@@ -4753,6 +4786,7 @@ int merge_owned_impl(ec_session *s, const void *d_records, uint64_t n, int k, in
     }
     s->no_index = false;
     EC_CHECK(rc);
+    s->clip_why = CLIP_WHY_STEPWISE;
     s->n_dense = U;
     s->dense_ok = true;
     collect_timing(s);
@@ -4913,6 +4947,7 @@ int ec_graph_load(ec_session *s, const void *d_records, uint64_t n, int k, unsig
     }
     s->n_dense = U;
     s->graph_loaded = true;
+    s->clip_why = CLIP_WHY_STEPWISE;
     collect_timing(s);
     s->stats_ok = true;
     return EC_OK;
@@ -5418,3 +5453,109 @@ int ec_assemble_from_kmers(ec_session *s, const char *kmers, const uint32_t *cou
 }
 
 }  // extern "C"
+
+// ---- tip clipping (clip.h) ---------------------------------------------------------------------
+namespace {
+
+// the rule on the session's current results: the clipped contigs into clip_list, their count and
+// k-mer windows into tot (the round's only read-back)
+int clip_evaluate(ec_session *s, unsigned int nc, unsigned long long max_len, ClipTotals &tot) {
+    hipStream_t st = s->stream;
+    tot = ClipTotals{};
+    if (!nc) return EC_OK;
+    EC_CHECK(s->clip_cand.ensure(nc));
+    EC_CHECK(s->clip_list.ensure((size_t)nc * 4));
+    EC_CHECK(s->clip_tot.ensure(sizeof(ClipTotals)));
+    EC_HIP(hipMemsetAsync(s->clip_tot.p, 0, sizeof(ClipTotals), st));
+    k_clip_cand<<<grid_for(nc, 256), 256, 0, st>>>(s->coff.as<unsigned long long>(), s->lcnt.as<unsigned int>(), nc,
+                                                   max_len, s->clip_cand.as<uint8_t>());
+    k_clip_pick<<<grid_for(nc, 256), 256, 0, st>>>(s->coff.as<unsigned long long>(), s->lk.as<long long>(),
+                                                   s->lcnt.as<unsigned int>(), s->clip_cand.as<uint8_t>(), nc, s->k,
+                                                   s->clip_list.as<unsigned int>(), s->clip_tot.as<ClipTotals>());
+    EC_CHECK(d2h(s, &tot, s->clip_tot.p, sizeof(ClipTotals), st));
+    return host_sync(s, st);
+}
+
+// one clipping round: the listed contigs' k-mers marked, the dense arrays exported with the marked
+// records as fillers into recs2 (as ec_assemble_from_kmers holds its records), then the merge and
+// the graph phase of ec_assemble_from_solid on them.  The index is read before the merge rewrites
+// it; recs2 is no scratch of the merge or the graph phase, and nothing else crosses the round.
+template <typename Ops, typename Index>
+int clip_round(ec_session *s, const Index &idx, unsigned int n_clip, unsigned int U) {
+    using K = typename Ops::K;
+    using Rec = typename RecOf<K>::T;
+    hipStream_t st = s->stream;
+    const int k = s->k;
+    EC_CHECK(s->clip_kill.ensure(std::max<size_t>(U, 1)));
+    EC_CHECK(s->recs2.ensure(std::max<size_t>((size_t)U * sizeof(Rec), 16)));
+    EC_HIP(hipMemsetAsync(s->clip_kill.p, 0, std::max<size_t>(U, 1), st));
+    k_clip_kill<Ops, Index><<<grid_for((uint64_t)n_clip * 64, 256), 256, 0, st>>>(
+        idx, s->clip_list.as<unsigned int>(), n_clip, s->coff.as<unsigned long long>(), s->chars.as<char>(), k, U,
+        s->clip_kill.as<uint8_t>());
+    k_clip_export<K><<<grid_for(U, 256), 256, 0, st>>>(s->dkey.as<K>(), s->dcnt.as<unsigned int>(),
+                                                       s->dfc.as<unsigned long long>(),
+                                                       s->dft.as<unsigned long long>(), s->clip_kill.as<uint8_t>(), U,
+                                                       s->recs2.as<Rec>());
+    // from here the call starts from inputs: the counting fields of the stats stay the assembly's
+    const ec_stats was = s->stats;
+    const unsigned flags = s->flags & ~(EC_FLAG_TIMING | EC_FLAG_KERNEL_TIMING);
+    EC_CHECK(begin_call(s, k, flags));
+    unsigned int U2 = 0;
+    Index sidx{};
+    if constexpr (std::is_same<Index, SolidIndexW>::value)
+        EC_CHECK(phase_merge_w(s, s->recs2.as<AggW>(), U, LLONG_MIN, U2, sidx));
+    else
+        EC_CHECK(phase_merge(s, s->recs2.as<Agg>(), U, LLONG_MIN, U2, sidx));
+    EC_CHECK((phase_graph<Ops, Index>(s, k, U2, sidx)));
+    ec_stats &now = s->stats;
+    now.n_reads = was.n_reads;
+    now.n_positions = was.n_positions;
+    now.n_distinct_est = was.n_distinct_est;
+    now.n_distinct = was.n_distinct;
+    now.table_capacity = was.table_capacity;
+    now.table_retries = was.table_retries;
+    now.n_records = was.n_records;
+    now.count_path = was.count_path;
+    now.count_variant = was.count_variant;
+    now.n_buckets = was.n_buckets;
+    now.record_bytes = was.record_bytes;
+    return EC_OK;
+}
+
+}  // namespace
+
+extern "C" int ec_clip_tips(ec_session *s, uint32_t max_tip_len, uint32_t max_rounds, ec_clip_info *info) {
+    if (!s || !info) {
+        set_error("ec_clip_tips: null session / info");
+        return EC_ERR_ARG;
+    }
+    if (max_rounds == 0) {
+        set_error("ec_clip_tips: max_rounds = 0");
+        return EC_ERR_ARG;
+    }
+    if (!s->clip_ok) {
+        set_error("ec_clip_tips needs the device state of a one-GPU assembly (ec_assemble_*, _from_solid, "
+                  "_from_kmers, ec_clip_tips): %s", s->clip_why);
+        return EC_ERR_STATE;
+    }
+    EC_HIP(hipSetDevice(s->device));
+    drop_step_state(s);
+    s->dense_ok = false;
+    *info = ec_clip_info{};
+    const unsigned long long max_len = max_tip_len ? max_tip_len : 2ull * (unsigned)s->k;
+    for (uint32_t r = 0; r < max_rounds; r++) {
+        ClipTotals tot{};
+        EC_CHECK(clip_evaluate(s, (unsigned int)s->stats.n_contigs, max_len, tot));
+        if (!tot.n_clip) {
+            info->converged = 1;
+            break;
+        }
+        const unsigned int U = (unsigned int)s->stats.n_solid;
+        if (s->k > 32) EC_CHECK((clip_round<OpsW, SolidIndexW>(s, s->cidxw, tot.n_clip, U)));
+        else EC_CHECK((clip_round<Ops64, SolidIndex>(s, s->cidx, tot.n_clip, U)));
+        info->rounds++;
+        info->n_tip_contigs += tot.n_clip;
+        info->n_tip_kmers += tot.n_kmer;
+    }
+    return EC_OK;
+}

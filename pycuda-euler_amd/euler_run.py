@@ -15,7 +15,9 @@ the outputs.  With one process the fused single-GPU path runs instead (--sharded
 path at any world size).  --backend gloo with --device N puts every rank on GPU N, the
 collectives staged through host memory (tests: several ranks of the real engine on one GPU).
 Contigs equal referenceAssembler.all_contigs(build(reads, k, limit), k) with reads parsed as
---fasta-mode says.
+--fasta-mode says.  --clip-tips (one process, fused path) goes beyond the reference: tips are
+clipped on the device (eulerhip.Session.clip_tips; --tip-len, --tip-rounds) before the outputs
+are written, and the ClipInfo line goes to stderr.
 """
 import argparse
 import os
@@ -43,7 +45,20 @@ def main(argv=None):
                     help="torch.distributed backend (nccl = RCCL over xGMI; gloo stages through host memory)")
     ap.add_argument("--device", type=int, default=-1, help="GPU of every rank (default: LOCAL_RANK)")
     ap.add_argument("--sharded", action="store_true", help="the sharded path even with one process")
+    ap.add_argument("--clip-tips", action="store_true",
+                    help="clip tips (short dead-end contigs beside a longer branch) after the assembly; "
+                         "one process, fused path only")
+    ap.add_argument("--tip-len", type=int, default=0, help="longest tip clipped, in characters (default 2 k)")
+    ap.add_argument("--tip-rounds", type=int, default=4, help="clipping rounds at most (default 4)")
     a = ap.parse_args(argv)
+    if a.clip_tips and (a.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        # (the junction-partitioned graph of the sharded path holds no complete link table)
+        print("euler_run: --clip-tips works on the one-process fused path only, not with --sharded or "
+              "several ranks", file=sys.stderr)
+        return 2
+    if a.clip_tips and (a.tip_len < 0 or a.tip_rounds < 1):
+        print("euler_run: --tip-len must be >= 0 and --tip-rounds >= 1", file=sys.stderr)
+        return 2
 
     import torch
 
@@ -70,7 +85,15 @@ def main(argv=None):
     if not sharded:
         sess = eulerhip.Session(local, stream=torch.cuda.current_stream().cuda_stream)
         sess.run_device(d_buf.data_ptr(), d_off.data_ptr(), hi - lo, a.k, a.limit, 0)
-        res = sess.fetch(a.k)
+        if a.clip_tips:
+            n0 = sess.stats().n_contigs
+            res, ci = sess.clip_tips(a.k, a.tip_len, a.tip_rounds)
+            if rank == 0:
+                print("clip-tips: rounds %d  converged %d  tip contigs %d  tip k-mers %d  contigs %d -> %d"
+                      % (ci["rounds"], ci["converged"], ci["n_tip_contigs"], ci["n_tip_kmers"], n0,
+                         res.stats.n_contigs), file=sys.stderr)
+        else:
+            res = sess.fetch(a.k)
         P = res.stats.n_positions
     else:
         import torch.distributed as dist

@@ -86,6 +86,19 @@ class Stats(ctypes.Structure):
         return d
 
 
+class ClipInfo(ctypes.Structure):
+    """ec_clip_info: what ec_clip_tips did"""
+    _fields_ = [
+        ("rounds", ctypes.c_uint32),
+        ("converged", ctypes.c_uint32),
+        ("n_tip_contigs", ctypes.c_uint64),
+        ("n_tip_kmers", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 _lib = None
 
 # exported symbols and their signatures (tests check that every one declared in
@@ -115,6 +128,7 @@ _SIGS = {
     "ec_copy_contigs": (ctypes.c_int, [_P, _P, _P]),
     "ec_copy_links": (ctypes.c_int, [_P, _P, _P]),
     "ec_copy_dict": (ctypes.c_int, [_P, _P, _P]),
+    "ec_clip_tips": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ClipInfo)]),
 }
 
 
@@ -383,9 +397,10 @@ class Session:
         self.run_host(buf, off, k, limit, flags)
         return self.fetch(k, want_dict)
 
-    def assemble_dict(self, d, k):
+    def assemble_dict(self, d, k, keep_dict=False):
         """all_contigs on a caller's dict {k-mer: count} (dict order matters): the graph phase
-        of the fused path, on the device (ec_assemble_from_kmers)."""
+        of the fused path, on the device (ec_assemble_from_kmers).  keep_dict: the session can
+        render the dict again (EC_FLAG_WANT_DICT), as clip_tips(want_dict=True) needs."""
         items = list(d.items())
         n = len(items)
         for x, _ in items:
@@ -393,8 +408,20 @@ class Session:
                 raise EulerHipError(EC_ERR_ARG, "dict key %r is not a %d-mer" % (x, k))
         km = "".join(x for x, _ in items).encode("ascii")
         cnt = np.array([c for _, c in items], dtype=np.uint32) if n else np.zeros(1, np.uint32)
-        check(lib().ec_assemble_from_kmers(self._h, km, cnt.ctypes.data, n, int(k), 0))
+        check(lib().ec_assemble_from_kmers(self._h, km, cnt.ctypes.data, n, int(k),
+                                           EC_FLAG_WANT_DICT if keep_dict else 0))
         return self.fetch(k)
+
+    def clip_tips(self, k, max_tip_len=0, max_rounds=4, want_dict=False):
+        """Clip the tips of the session's current assembly (ec_clip_tips; the rule is in
+        include/eulerhip.h): short dead-end contigs that have a longer, or equal and earlier,
+        sibling at their junction lose their k-mers, and the graph phase runs again, up to
+        max_rounds times.  max_tip_len in characters, 0 = 2 k.  Returns (Result, info) with info
+        = {rounds, converged, n_tip_contigs, n_tip_kmers}; want_dict needs an assembly run with
+        EC_FLAG_WANT_DICT."""
+        ci = ClipInfo()
+        check(lib().ec_clip_tips(self._h, int(max_tip_len), int(max_rounds), ctypes.byref(ci)))
+        return self.fetch(k, want_dict), ci.as_dict()
 
 
 _default = {}
