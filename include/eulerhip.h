@@ -217,7 +217,8 @@ int ec_copy_dict(ec_session *s, char *kmers, uint32_t *counts);
  * n_records, table_*); timing fields are unspecified.  A call whose first evaluation finds no tip
  * leaves every result byte as it was (rounds = 0, converged = 1).
  * Valid after a successful ec_assemble_device / _host / _packed_host / _staged / _packed_reads,
- * ec_assemble_from_solid, ec_assemble_from_kmers or ec_clip_tips, on standard-alphabet results.
+ * ec_assemble_from_solid, ec_assemble_from_kmers, ec_clip_tips or ec_pop_bubbles, on
+ * standard-alphabet results.
  * Refused before touching the device (the session stays usable, earlier results fetchable):
  * EC_ERR_ARG for a NULL session or info or max_rounds = 0; EC_ERR_STATE, ec_last_error naming the
  * case, on a new session, after ec_session_trim, after the stepwise calls (ec_count_shard,
@@ -229,6 +230,39 @@ typedef struct {
     uint64_t n_tip_kmers;   /* canonical k-mers removed, all rounds                     */
 } ec_clip_info;
 int ec_clip_tips(ec_session *s, uint32_t max_tip_len, uint32_t max_rounds, ec_clip_info *info);
+
+/* Bubble popping on the session's results (csrc/pop.h) -- the second clean-up beyond the
+ * reference: of parallel short branches between the same two contig ends the best covered one
+ * survives.  With (G, r) the session's current all_contigs result and d its dict, per contig i
+ * len_i = len(r[i]), W_i = len_i - k + 1 and S_i = the sum of d[r[i][p:p+k]] over its W_i windows
+ * (dict counts: a palindromic k-mer's count already holds 2 per occurrence); max_bubble_len in
+ * characters (0: 2 k; a SNP branch is k k-mers, 2 k - 1 characters):
+ *   - a link (j, o) reaches the port (j, t), t = 1 if o == '+' else 0 (the side rule of the tip
+ *     rule's siblings);
+ *   - contig i is a branch iff len_i <= max_bubble_len, |G[i][0]| == 1 and |G[i][1]| == 1, its two
+ *     ports P0 and P1 differ and neither port's contig is i itself;
+ *   - contig i2 != i is a partner of i iff it is a branch and its unordered pair of ports equals
+ *     {P0, P1} (it may run in the opposite orientation);
+ *   - i is popped iff some partner i2 has S_i2 * W_i > S_i * W_i2 (a strictly higher mean
+ *     coverage, compared exactly in integers), or equality there and i2 < i: of any number of
+ *     parallel branches exactly one survives, so the two ports stay connected;
+ *   - popping removes every k-mer window of r[i], and its twin, from the dict; the order (first
+ *     events) of the remaining entries is unchanged.
+ * The loop, the results and stats the session then holds, the no-op guarantee (a first evaluation
+ * that finds nothing leaves every result byte as it was: rounds = 0, converged = 1) and the
+ * refusals are those of ec_clip_tips; after either call ec_clip_tips, ec_pop_bubbles and
+ * ec_copy_contig_kmer_sums are valid again, in any order.  Additionally EC_ERR_ARG for
+ * max_bubble_len > 65535: the cap keeps S * W below 2^64 (S < 2^32 W and W < 2^16). */
+typedef struct {
+    uint32_t rounds;           /* rounds that popped >= 1 contig (= graph phases re-run)   */
+    uint32_t converged;        /* 1: the last evaluation found no bubble                   */
+    uint64_t n_bubble_contigs; /* contigs popped, all rounds                               */
+    uint64_t n_bubble_kmers;   /* canonical k-mers removed, all rounds                     */
+} ec_pop_info;
+int ec_pop_bubbles(ec_session *s, uint32_t max_bubble_len, uint32_t max_rounds, ec_pop_info *info);
+/* sums[n_contigs]: S_i of the session's current contigs.  Valid and refused as ec_clip_tips
+ * (EC_ERR_ARG for a NULL session or sums); changes no state. */
+int ec_copy_contig_kmer_sums(ec_session *s, uint64_t *sums);
 
 /* ---- layer 2: per-module drop-ins (host buffers, one H2D/D2H round trip per call) ---------
  * Each restates the INTENDED semantics of the reference PyCUDA function named; the reference's
@@ -407,7 +441,7 @@ int ec_count_shard(ec_session *s, const uint8_t *d_reads, const uint64_t *d_offs
 /* CALL ORDER of the stepwise calls from here to the end of this header.  A session holds one
  * piece of device state at a time, and every call that starts from inputs -- ec_assemble_*,
  * ec_count_shard, ec_merge_owned*, ec_assemble_from_solid / _from_kmers, ec_graph_load*,
- * ec_clip_tips (its own inputs are the results of the assembly before it) -- and
+ * ec_clip_tips / ec_pop_bubbles (their inputs are the results of the assembly before them) -- and
  * ec_session_trim (any min_bytes) replace or release it.  A call that needs state which is gone,
  * or was never made, is refused before it touches the device, ec_last_error says why, and the
  * session stays usable:

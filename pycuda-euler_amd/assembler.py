@@ -13,6 +13,8 @@ through libeulerhip.so:
 * assemble(reads, k, limit) -> (d, G, r) in one fused device pass (no dict round trip);
 * clip_tips(d, k) -> (d2, G, r): tip clipping on the device, which the reference does not have
   (also assemble(..., clip_tips=True); off by default);
+* pop_bubbles(d, k) -> (d2, G, r): bubble popping on the device, likewise beyond the reference
+  (also assemble(..., pop_bubbles=True); off by default; with both, tips are clipped first);
 * print_GFA / print_dbg (:115-130, with the working formatting of tests/referenceAssembler.py:119-134);
 * twin / kmers / fw / bw / contig_to_string: the reference's string helpers (host, not on
   the hot path).
@@ -75,13 +77,16 @@ def all_contigs(d, k, session=None):
     return res.G(), res.contigs
 
 
-def assemble(reads, k=31, limit=1, session=None, want_dict=True, clip_tips=False):
-    """build + all_contigs in one device pass: (d, G, r).  clip_tips: the tips clipped at the
-    default settings (see clip_tips below; beyond the reference) -- d is then the clipped dict."""
+def assemble(reads, k=31, limit=1, session=None, want_dict=True, clip_tips=False, pop_bubbles=False):
+    """build + all_contigs in one device pass: (d, G, r).  clip_tips / pop_bubbles: the tips
+    clipped, then the bubbles popped, at the default settings (see clip_tips and pop_bubbles
+    below; beyond the reference) -- d is then the cleaned dict."""
     s = _session(session)
     res = s.assemble(list(reads), int(k), limit=limit, want_dict=want_dict)
     if clip_tips:
         res, _ = s.clip_tips(int(k), want_dict=want_dict)
+    if pop_bubbles:
+        res, _ = s.pop_bubbles(int(k), want_dict=want_dict)
     d = collections.OrderedDict(res.dict_items) if want_dict else None
     return d, res.G(), res.contigs
 
@@ -95,6 +100,19 @@ def clip_tips(d, k, max_tip_len=None, max_rounds=4, session=None):
     s = _session(session)
     s.assemble_dict(d, int(k), keep_dict=True)
     res, _ = s.clip_tips(int(k), max_tip_len or 0, max_rounds, want_dict=True)
+    return collections.OrderedDict(res.dict_items), res.G(), res.contigs
+
+
+def pop_bubbles(d, k, max_bubble_len=None, max_rounds=4, session=None):
+    """Graph clean-up the reference does not have: all_contigs(d, k), then the bubbles popped on
+    the device (eulerhip.Session.pop_bubbles; the rule is stated in include/eulerhip.h) -- of
+    parallel branches of at most max_bubble_len characters (None: 2 k) between the same two
+    contig ends only the one with the highest mean count in d, or the earliest of equals, stays,
+    up to max_rounds rounds.  Returns (d2, G, r): the surviving dict in d's order and
+    all_contigs(d2, k)."""
+    s = _session(session)
+    s.assemble_dict(d, int(k), keep_dict=True)
+    res, _ = s.pop_bubbles(int(k), max_bubble_len or 0, max_rounds, want_dict=True)
     return collections.OrderedDict(res.dict_items), res.G(), res.contigs
 
 

@@ -45,6 +45,7 @@
 #include "junction.h"
 #include "join_local.h"
 #include "clip.h"
+#include "pop.h"
 
 #include <atomic>
 #include <chrono>
@@ -361,6 +362,8 @@ struct ec_session {
     SolidIndex cidx{};
     SolidIndexW cidxw{};
     DevBuf clip_cand, clip_list, clip_kill, clip_tot;
+    // ec_pop_bubbles / ec_copy_contig_kmer_sums (pop.h): branch keys, per-contig sums, the tile table
+    DevBuf pop_key, pop_sum, pop_tcnt, pop_toff, pop_tile;
 };
 
 // ec_clip_tips' refusal after the stepwise calls (ec_session::clip_why)
@@ -4270,7 +4273,8 @@ static void for_each_buf(ec_session *s, Fn fn) {
                      &s->skm_rec, &s->skm_ev, &s->skm_end, &s->wcodes_tab,
                      &s->run_cnt, &s->run_ends, &s->run_dends, &s->rt_lb,
                      &s->jl_kof, &s->jl_rs, &s->jl_re, &s->jl_cnt, &s->jl_off, &s->jl_flag, &s->rpack,
-                     &s->clip_cand, &s->clip_list, &s->clip_kill, &s->clip_tot};
+                     &s->clip_cand, &s->clip_list, &s->clip_kill, &s->clip_tot,
+                     &s->pop_key, &s->pop_sum, &s->pop_tcnt, &s->pop_toff, &s->pop_tile};
     for (auto *b : all) fn(*b);
 }
 
@@ -5522,6 +5526,97 @@ int clip_round(ec_session *s, const Index &idx, unsigned int n_clip, unsigned in
     return EC_OK;
 }
 
+// ---- bubble popping, per-contig k-mer count sums (pop.h) ----------------------------------------
+// S_i of the contigs (sel: only of those whose sel[i] is not POP_NONE) into pop_sum, on the stream
+template <typename Ops, typename Index>
+int ksum_run(ec_session *s, const Index &idx, unsigned int nc, const unsigned long long *sel) {
+    hipStream_t st = s->stream;
+    const unsigned int U = (unsigned int)s->stats.n_solid;
+    // every contig has at most ceil(W / KSUM_TILE) <= 1 + chars / KSUM_TILE tiles
+    const unsigned long long cap = (unsigned long long)nc + s->stats.n_contig_chars / KSUM_TILE + 1;
+    if (cap >= (1ull << 32)) {
+        set_error("contig k-mer sums: %llu tiles at most, >= 2^32", cap);
+        return EC_ERR_CAPACITY;
+    }
+    EC_CHECK(s->pop_sum.ensure((size_t)nc * 8));
+    EC_CHECK(s->pop_tcnt.ensure((size_t)nc * 4));
+    EC_CHECK(s->pop_toff.ensure((size_t)nc * 4));
+    EC_CHECK(s->pop_tile.ensure((size_t)cap * 4));
+    EC_HIP(hipMemsetAsync(s->pop_sum.p, 0, (size_t)nc * 8, st));
+    EC_HIP(hipMemsetAsync(s->pop_tile.p, 0xFF, (size_t)cap * 4, st));  // (no contig: the tile is skipped)
+    k_ksum_count<<<grid_for(nc, 256), 256, 0, st>>>(s->coff.as<unsigned long long>(), nc, s->k, sel,
+                                                    s->pop_tcnt.as<unsigned int>());
+    EC_CHECK(scan_excl_u32(s, s->pop_tcnt.as<unsigned int>(), s->pop_toff.as<unsigned int>(), nc));
+    k_ksum_tiles<<<grid_for((uint64_t)nc * 64, 256), 256, 0, st>>>(s->pop_tcnt.as<unsigned int>(),
+                                                                   s->pop_toff.as<unsigned int>(), nc,
+                                                                   (unsigned int)cap, s->pop_tile.as<unsigned int>());
+    k_contig_ksum<Ops, Index><<<(unsigned int)((cap + 3) / 4), 256, 0, st>>>(
+        idx, s->pop_tile.as<unsigned int>(), s->pop_toff.as<unsigned int>(), (unsigned int)cap, nc,
+        s->coff.as<unsigned long long>(), s->chars.as<char>(), s->dcnt.as<unsigned int>(), s->k, U,
+        s->pop_sum.as<unsigned long long>());
+    EC_HIP(hipGetLastError());
+    return EC_OK;
+}
+
+int ksum_any(ec_session *s, unsigned int nc, const unsigned long long *sel) {
+    if (s->k > 32) return ksum_run<OpsW, SolidIndexW>(s, s->cidxw, nc, sel);
+    return ksum_run<Ops64, SolidIndex>(s, s->cidx, nc, sel);
+}
+
+// the bubble rule on the session's current results, as clip_evaluate: popped contigs into clip_list
+int pop_evaluate(ec_session *s, unsigned int nc, unsigned long long max_len, ClipTotals &tot) {
+    hipStream_t st = s->stream;
+    tot = ClipTotals{};
+    if (!nc) return EC_OK;
+    EC_CHECK(s->pop_key.ensure((size_t)nc * 8));
+    EC_CHECK(s->clip_list.ensure((size_t)nc * 4));
+    EC_CHECK(s->clip_tot.ensure(sizeof(ClipTotals)));
+    EC_HIP(hipMemsetAsync(s->clip_tot.p, 0, sizeof(ClipTotals), st));
+    k_pop_cand<<<grid_for(nc, 256), 256, 0, st>>>(s->coff.as<unsigned long long>(), s->lk.as<long long>(),
+                                                  s->lcnt.as<unsigned int>(), nc, max_len,
+                                                  s->pop_key.as<unsigned long long>());
+    EC_CHECK(ksum_any(s, nc, s->pop_key.as<unsigned long long>()));
+    k_pop_pick<<<grid_for(nc, 256), 256, 0, st>>>(s->coff.as<unsigned long long>(), s->lk.as<long long>(),
+                                                  s->lcnt.as<unsigned int>(), s->pop_key.as<unsigned long long>(),
+                                                  s->pop_sum.as<unsigned long long>(), nc, s->k,
+                                                  s->clip_list.as<unsigned int>(), s->clip_tot.as<ClipTotals>());
+    EC_CHECK(d2h(s, &tot, s->clip_tot.p, sizeof(ClipTotals), st));
+    return host_sync(s, st);
+}
+
+// the loop of ec_clip_tips and ec_pop_bubbles: evaluate the rule, stop if it lists nothing, else
+// remove the listed contigs' k-mers and run the graph phase again (clip_round)
+template <typename Eval>
+int cleanup_loop(ec_session *s, uint32_t max_rounds, Eval eval, uint32_t &rounds, uint32_t &converged,
+                 uint64_t &n_contigs, uint64_t &n_kmers) {
+    EC_HIP(hipSetDevice(s->device));
+    drop_step_state(s);
+    s->dense_ok = false;
+    for (uint32_t r = 0; r < max_rounds; r++) {
+        ClipTotals tot{};
+        EC_CHECK(eval((unsigned int)s->stats.n_contigs, tot));
+        if (!tot.n_clip) {
+            converged = 1;
+            break;
+        }
+        const unsigned int U = (unsigned int)s->stats.n_solid;
+        if (s->k > 32) EC_CHECK((clip_round<OpsW, SolidIndexW>(s, s->cidxw, tot.n_clip, U)));
+        else EC_CHECK((clip_round<Ops64, SolidIndex>(s, s->cidx, tot.n_clip, U)));
+        rounds++;
+        n_contigs += tot.n_clip;
+        n_kmers += tot.n_kmer;
+    }
+    return EC_OK;
+}
+
+// the refusals ec_clip_tips, ec_pop_bubbles and ec_copy_contig_kmer_sums share
+int clip_state_check(ec_session *s, const char *who) {
+    if (s->clip_ok) return EC_OK;
+    set_error("%s needs the device state of a one-GPU assembly (ec_assemble_*, _from_solid, _from_kmers, "
+              "ec_clip_tips, ec_pop_bubbles): %s", who, s->clip_why);
+    return EC_ERR_STATE;
+}
+
 }  // namespace
 
 extern "C" int ec_clip_tips(ec_session *s, uint32_t max_tip_len, uint32_t max_rounds, ec_clip_info *info) {
@@ -5533,29 +5628,45 @@ extern "C" int ec_clip_tips(ec_session *s, uint32_t max_tip_len, uint32_t max_ro
         set_error("ec_clip_tips: max_rounds = 0");
         return EC_ERR_ARG;
     }
-    if (!s->clip_ok) {
-        set_error("ec_clip_tips needs the device state of a one-GPU assembly (ec_assemble_*, _from_solid, "
-                  "_from_kmers, ec_clip_tips): %s", s->clip_why);
-        return EC_ERR_STATE;
-    }
-    EC_HIP(hipSetDevice(s->device));
-    drop_step_state(s);
-    s->dense_ok = false;
+    EC_CHECK(clip_state_check(s, "ec_clip_tips"));
     *info = ec_clip_info{};
     const unsigned long long max_len = max_tip_len ? max_tip_len : 2ull * (unsigned)s->k;
-    for (uint32_t r = 0; r < max_rounds; r++) {
-        ClipTotals tot{};
-        EC_CHECK(clip_evaluate(s, (unsigned int)s->stats.n_contigs, max_len, tot));
-        if (!tot.n_clip) {
-            info->converged = 1;
-            break;
-        }
-        const unsigned int U = (unsigned int)s->stats.n_solid;
-        if (s->k > 32) EC_CHECK((clip_round<OpsW, SolidIndexW>(s, s->cidxw, tot.n_clip, U)));
-        else EC_CHECK((clip_round<Ops64, SolidIndex>(s, s->cidx, tot.n_clip, U)));
-        info->rounds++;
-        info->n_tip_contigs += tot.n_clip;
-        info->n_tip_kmers += tot.n_kmer;
+    return cleanup_loop(
+        s, max_rounds, [&](unsigned int nc, ClipTotals &tot) { return clip_evaluate(s, nc, max_len, tot); },
+        info->rounds, info->converged, info->n_tip_contigs, info->n_tip_kmers);
+}
+
+extern "C" int ec_pop_bubbles(ec_session *s, uint32_t max_bubble_len, uint32_t max_rounds, ec_pop_info *info) {
+    if (max_bubble_len > 65535) {
+        set_error("ec_pop_bubbles: max_bubble_len %u > 65535", max_bubble_len);
+        return EC_ERR_ARG;
     }
-    return EC_OK;
+    if (!s || !info) {
+        set_error("ec_pop_bubbles: null session / info");
+        return EC_ERR_ARG;
+    }
+    if (max_rounds == 0) {
+        set_error("ec_pop_bubbles: max_rounds = 0");
+        return EC_ERR_ARG;
+    }
+    EC_CHECK(clip_state_check(s, "ec_pop_bubbles"));
+    *info = ec_pop_info{};
+    const unsigned long long max_len = max_bubble_len ? max_bubble_len : 2ull * (unsigned)s->k;
+    return cleanup_loop(
+        s, max_rounds, [&](unsigned int nc, ClipTotals &tot) { return pop_evaluate(s, nc, max_len, tot); },
+        info->rounds, info->converged, info->n_bubble_contigs, info->n_bubble_kmers);
+}
+
+extern "C" int ec_copy_contig_kmer_sums(ec_session *s, uint64_t *sums) {
+    if (!s || !sums) {
+        set_error("ec_copy_contig_kmer_sums: null session / sums");
+        return EC_ERR_ARG;
+    }
+    EC_CHECK(clip_state_check(s, "ec_copy_contig_kmer_sums"));
+    const unsigned int nc = (unsigned int)s->stats.n_contigs;
+    if (!nc) return EC_OK;
+    EC_HIP(hipSetDevice(s->device));
+    EC_CHECK(ksum_any(s, nc, nullptr));
+    EC_CHECK(d2h(s, sums, s->pop_sum.p, (size_t)nc * 8, s->stream));
+    return host_sync(s, s->stream);
 }

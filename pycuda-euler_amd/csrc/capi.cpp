@@ -84,4 +84,4 @@ bool memlog_on() {
 }  // namespace ec
 
 extern "C" const char *ec_last_error(void) { return ec::g_err; }
-extern "C" int ec_version(void) { return 200; /* 0.2.0: ec_clip_tips */ }
+extern "C" int ec_version(void) { return 300; /* 0.3.0: ec_pop_bubbles, ec_copy_contig_kmer_sums */ }

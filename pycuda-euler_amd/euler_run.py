@@ -17,7 +17,9 @@ collectives staged through host memory (tests: several ranks of the real engine 
 Contigs equal referenceAssembler.all_contigs(build(reads, k, limit), k) with reads parsed as
 --fasta-mode says.  --clip-tips (one process, fused path) goes beyond the reference: tips are
 clipped on the device (eulerhip.Session.clip_tips; --tip-len, --tip-rounds) before the outputs
-are written, and the ClipInfo line goes to stderr.
+are written, and the ClipInfo line goes to stderr.  --pop-bubbles (same path) pops bubbles
+(eulerhip.Session.pop_bubbles; --bubble-len, --bubble-rounds), after the tips if both are given,
+and the PopInfo line goes to stderr.
 """
 import argparse
 import os
@@ -50,6 +52,12 @@ def main(argv=None):
                          "one process, fused path only")
     ap.add_argument("--tip-len", type=int, default=0, help="longest tip clipped, in characters (default 2 k)")
     ap.add_argument("--tip-rounds", type=int, default=4, help="clipping rounds at most (default 4)")
+    ap.add_argument("--pop-bubbles", action="store_true",
+                    help="pop bubbles (of parallel short branches the best covered one stays) after the "
+                         "assembly and after --clip-tips; one process, fused path only")
+    ap.add_argument("--bubble-len", type=int, default=0,
+                    help="longest branch popped, in characters (default 2 k; at most 65535)")
+    ap.add_argument("--bubble-rounds", type=int, default=4, help="popping rounds at most (default 4)")
     a = ap.parse_args(argv)
     if a.clip_tips and (a.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         # (the junction-partitioned graph of the sharded path holds no complete link table)
@@ -58,6 +66,13 @@ def main(argv=None):
         return 2
     if a.clip_tips and (a.tip_len < 0 or a.tip_rounds < 1):
         print("euler_run: --tip-len must be >= 0 and --tip-rounds >= 1", file=sys.stderr)
+        return 2
+    if a.pop_bubbles and (a.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        print("euler_run: --pop-bubbles works on the one-process fused path only, not with --sharded or "
+              "several ranks", file=sys.stderr)
+        return 2
+    if a.pop_bubbles and (not 0 <= a.bubble_len <= 65535 or a.bubble_rounds < 1):
+        print("euler_run: --bubble-len must be in 0 .. 65535 and --bubble-rounds >= 1", file=sys.stderr)
         return 2
 
     import torch
@@ -92,7 +107,14 @@ def main(argv=None):
                 print("clip-tips: rounds %d  converged %d  tip contigs %d  tip k-mers %d  contigs %d -> %d"
                       % (ci["rounds"], ci["converged"], ci["n_tip_contigs"], ci["n_tip_kmers"], n0,
                          res.stats.n_contigs), file=sys.stderr)
-        else:
+        if a.pop_bubbles:
+            n0 = sess.stats().n_contigs
+            res, pi = sess.pop_bubbles(a.k, a.bubble_len, a.bubble_rounds)
+            if rank == 0:
+                print("pop-bubbles: rounds %d  converged %d  bubble contigs %d  bubble k-mers %d  contigs %d -> %d"
+                      % (pi["rounds"], pi["converged"], pi["n_bubble_contigs"], pi["n_bubble_kmers"], n0,
+                         res.stats.n_contigs), file=sys.stderr)
+        if not a.clip_tips and not a.pop_bubbles:
             res = sess.fetch(a.k)
         P = res.stats.n_positions
     else:

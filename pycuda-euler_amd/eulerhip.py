@@ -99,6 +99,19 @@ class ClipInfo(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class PopInfo(ctypes.Structure):
+    """ec_pop_info: what ec_pop_bubbles did"""
+    _fields_ = [
+        ("rounds", ctypes.c_uint32),
+        ("converged", ctypes.c_uint32),
+        ("n_bubble_contigs", ctypes.c_uint64),
+        ("n_bubble_kmers", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 _lib = None
 
 # exported symbols and their signatures (tests check that every one declared in
@@ -129,6 +142,8 @@ _SIGS = {
     "ec_copy_links": (ctypes.c_int, [_P, _P, _P]),
     "ec_copy_dict": (ctypes.c_int, [_P, _P, _P]),
     "ec_clip_tips": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ClipInfo)]),
+    "ec_pop_bubbles": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(PopInfo)]),
+    "ec_copy_contig_kmer_sums": (ctypes.c_int, [_P, _P]),
 }
 
 
@@ -422,6 +437,24 @@ class Session:
         ci = ClipInfo()
         check(lib().ec_clip_tips(self._h, int(max_tip_len), int(max_rounds), ctypes.byref(ci)))
         return self.fetch(k, want_dict), ci.as_dict()
+
+    def pop_bubbles(self, k, max_bubble_len=0, max_rounds=4, want_dict=False):
+        """Pop the bubbles of the session's current assembly (ec_pop_bubbles; the rule is in
+        include/eulerhip.h): of parallel branches of at most max_bubble_len characters (0 = 2 k)
+        between the same two contig ends the one with the highest mean k-mer count, or the
+        earliest of equals, survives; the others lose their k-mers and the graph phase runs again,
+        up to max_rounds times.  Returns (Result, info) with info = {rounds, converged,
+        n_bubble_contigs, n_bubble_kmers}; want_dict needs an assembly run with EC_FLAG_WANT_DICT."""
+        pi = PopInfo()
+        check(lib().ec_pop_bubbles(self._h, int(max_bubble_len), int(max_rounds), ctypes.byref(pi)))
+        return self.fetch(k, want_dict), pi.as_dict()
+
+    def contig_kmer_sums(self):
+        """np.uint64[n_contigs]: per contig of the session's current assembly the sum of the dict
+        counts of its k-mer windows (ec_copy_contig_kmer_sums); changes no state."""
+        out = np.zeros(max(int(self.stats().n_contigs), 1), np.uint64)
+        check(lib().ec_copy_contig_kmer_sums(self._h, out.ctypes.data))
+        return out[:int(self.stats().n_contigs)]
 
 
 _default = {}
