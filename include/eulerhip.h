@@ -217,7 +217,7 @@ int ec_copy_dict(ec_session *s, char *kmers, uint32_t *counts);
  * n_records, table_*); timing fields are unspecified.  A call whose first evaluation finds no tip
  * leaves every result byte as it was (rounds = 0, converged = 1).
  * Valid after a successful ec_assemble_device / _host / _packed_host / _staged / _packed_reads,
- * ec_assemble_from_solid, ec_assemble_from_kmers, ec_clip_tips or ec_pop_bubbles, on
+ * ec_assemble_from_solid, ec_assemble_from_kmers, ec_clip_tips, ec_pop_bubbles or ec_refilter, on
  * standard-alphabet results.
  * Refused before touching the device (the session stays usable, earlier results fetchable):
  * EC_ERR_ARG for a NULL session or info or max_rounds = 0; EC_ERR_STATE, ec_last_error naming the
@@ -250,8 +250,9 @@ int ec_clip_tips(ec_session *s, uint32_t max_tip_len, uint32_t max_rounds, ec_cl
  *     events) of the remaining entries is unchanged.
  * The loop, the results and stats the session then holds, the no-op guarantee (a first evaluation
  * that finds nothing leaves every result byte as it was: rounds = 0, converged = 1) and the
- * refusals are those of ec_clip_tips; after either call ec_clip_tips, ec_pop_bubbles and
- * ec_copy_contig_kmer_sums are valid again, in any order.  Additionally EC_ERR_ARG for
+ * refusals are those of ec_clip_tips; after either call, and after ec_refilter, ec_clip_tips,
+ * ec_pop_bubbles, ec_copy_contig_kmer_sums, ec_kmer_spectrum and ec_refilter are valid again, in
+ * any order.  Additionally EC_ERR_ARG for
  * max_bubble_len > 65535: the cap keeps S * W below 2^64 (S < 2^32 W and W < 2^16). */
 typedef struct {
     uint32_t rounds;           /* rounds that popped >= 1 contig (= graph phases re-run)   */
@@ -263,6 +264,56 @@ int ec_pop_bubbles(ec_session *s, uint32_t max_bubble_len, uint32_t max_rounds, 
 /* sums[n_contigs]: S_i of the session's current contigs.  Valid and refused as ec_clip_tips
  * (EC_ERR_ARG for a NULL session or sums); changes no state. */
 int ec_copy_contig_kmer_sums(ec_session *s, uint64_t *sums);
+
+/* Coverage-aware solid threshold (csrc/spectrum.h) -- beyond the reference, whose build(limit) takes
+ * a number the caller must know: the k-mer count spectrum of the session's dict, a deterministic
+ * rule that reads the threshold off it, and a re-filter of the dict by a new limit that needs no
+ * recount. */
+#define EC_SPECTRUM_MAX_BINS 4096
+/* hist[nbins], 2 <= nbins <= EC_SPECTRUM_MAX_BINS: hist[c] = canonical solid k-mers of the session's
+ * current dict whose dict count is c (c < nbins-1); hist[nbins-1] = those with count >= nbins-1.
+ * sum(hist) == n_solid.  Counts are dict counts (a palindrome holds 2 per occurrence).
+ * Valid and refused as ec_copy_contig_kmer_sums (EC_ERR_ARG for a NULL session or hist or nbins out
+ * of range); changes no state. */
+int ec_kmer_spectrum(ec_session *s, uint32_t nbins, uint64_t *hist);
+
+/* The threshold rule, in integer arithmetic only, on h = hist[0 .. nbins-1]:
+ *   lo           the smallest c with h[c] > 0; none: not found;
+ *   descent_end  d = the smallest c in [lo, nbins-2] with h[c] < h[c+1]; not found if there is none
+ *                or d == lo (the spectrum does not start with a descent: the coverage is too low to
+ *                show an error slope above the assembly's own limit);
+ *   peak         p = argmax of h[c] over c in [d, nbins-1], the smallest c on ties; not found if
+ *                p == nbins-1 (the coverage peak sits in the saturating bin: more bins needed);
+ *   floor        m = the minimum of h[lo .. p];
+ *   limit        v = the smallest c in [lo, p] with EC_SPECTRUM_FLOOR_DIV * (h[c] - m) <= h[p] - m:
+ *                the first bin that has come down to within 1 / EC_SPECTRUM_FLOOR_DIV of the peak's
+ *                height above the floor -- of the bins that qualify, the leftmost removes the fewest
+ *                k-mers; not found if v == p.
+ * found = 1: limit = v, k-mers with count > v are kept (ec_refilter(s, v)).  Not found: found = 0,
+ * limit = 0, the other fields as far as they were computed, 0 otherwise.  EC_SPECTRUM_FLOOR_DIV is
+ * a design constant of the rule, not a measured tolerance.  Host only: no session, no device.
+ * EC_ERR_ARG for a NULL argument or nbins outside [2, EC_SPECTRUM_MAX_BINS]. */
+#define EC_SPECTRUM_FLOOR_DIV 16
+typedef struct { uint32_t found, lo, descent_end, peak, limit, pad; uint64_t floor; } ec_spectrum_info;
+int ec_spectrum_threshold(const uint64_t *hist, uint32_t nbins, ec_spectrum_info *info);
+
+/* Re-filter the session's current dict by a new solid limit without counting again: every k-mer
+ * (and its twin) whose dict count is <= limit is removed, the order (first events) of the rest is
+ * unchanged; the merge and the graph phase then run once on the remaining set, as one round of
+ * ec_clip_tips does.  ec_assemble_*(limit = 1) followed by ec_refilter(L) holds what
+ * ec_assemble_*(limit = L) holds: ec_copy_contigs / _links / _dict and ec_get_stats (its n_solid,
+ * n_dict, n_contigs, n_contig_chars, n_links beside the first assembly's counting fields, as after
+ * ec_clip_tips) deliver the results of the filtered dict.  n_removed_kmers counts canonical k-mers;
+ * changed = 1 iff at least one was removed.  If no k-mer has count <= limit (any limit at or below
+ * the assembly's own included) no result byte changes and changed = 0; a "low" limit is no error.
+ * Valid and refused as ec_clip_tips (EC_ERR_ARG for a NULL session or info), before the device is
+ * touched. */
+typedef struct {
+    uint32_t limit;           /* the limit applied                       */
+    uint32_t changed;         /* 1: k-mers were removed, the graph phase re-run */
+    uint64_t n_removed_kmers; /* canonical k-mers removed                */
+} ec_refilter_info;
+int ec_refilter(ec_session *s, uint32_t limit, ec_refilter_info *info);
 
 /* ---- layer 2: per-module drop-ins (host buffers, one H2D/D2H round trip per call) ---------
  * Each restates the INTENDED semantics of the reference PyCUDA function named; the reference's
@@ -441,7 +492,8 @@ int ec_count_shard(ec_session *s, const uint8_t *d_reads, const uint64_t *d_offs
 /* CALL ORDER of the stepwise calls from here to the end of this header.  A session holds one
  * piece of device state at a time, and every call that starts from inputs -- ec_assemble_*,
  * ec_count_shard, ec_merge_owned*, ec_assemble_from_solid / _from_kmers, ec_graph_load*,
- * ec_clip_tips / ec_pop_bubbles (their inputs are the results of the assembly before them) -- and
+ * ec_clip_tips / ec_pop_bubbles / ec_refilter (their inputs are the results of the assembly before
+ * them) -- and
  * ec_session_trim (any min_bytes) replace or release it.  A call that needs state which is gone,
  * or was never made, is refused before it touches the device, ec_last_error says why, and the
  * session stays usable:

@@ -15,6 +15,11 @@ through libeulerhip.so:
   (also assemble(..., clip_tips=True); off by default);
 * pop_bubbles(d, k) -> (d2, G, r): bubble popping on the device, likewise beyond the reference
   (also assemble(..., pop_bubbles=True); off by default; with both, tips are clipped first);
+* assemble(..., auto_limit=True): beyond the reference, the solid limit read off the k-mer count
+  spectrum of the assembly (eulerhip.spectrum_threshold) and applied on the device without a
+  recount, before the tips and bubbles (off by default);
+* kmer_spectrum(reads, k, limit) -> the count spectrum of build(reads, k, limit), beyond the
+  reference;
 * print_GFA / print_dbg (:115-130, with the working formatting of tests/referenceAssembler.py:119-134);
 * twin / kmers / fw / bw / contig_to_string: the reference's string helpers (host, not on
   the hot path).
@@ -77,18 +82,32 @@ def all_contigs(d, k, session=None):
     return res.G(), res.contigs
 
 
-def assemble(reads, k=31, limit=1, session=None, want_dict=True, clip_tips=False, pop_bubbles=False):
-    """build + all_contigs in one device pass: (d, G, r).  clip_tips / pop_bubbles: the tips
-    clipped, then the bubbles popped, at the default settings (see clip_tips and pop_bubbles
-    below; beyond the reference) -- d is then the cleaned dict."""
+def assemble(reads, k=31, limit=1, session=None, want_dict=True, clip_tips=False, pop_bubbles=False,
+             auto_limit=False):
+    """build + all_contigs in one device pass: (d, G, r).  auto_limit: the solid limit the k-mer
+    count spectrum of the assembly suggests (eulerhip.spectrum_threshold) applied first, if one
+    is found.  clip_tips / pop_bubbles: the tips clipped, then the bubbles popped, at the default
+    settings (see clip_tips and pop_bubbles below).  All three go beyond the reference -- d is
+    then the cleaned dict."""
     s = _session(session)
     res = s.assemble(list(reads), int(k), limit=limit, want_dict=want_dict)
+    if auto_limit:
+        res, _, _ = s.auto_limit(int(k), want_dict=want_dict)
     if clip_tips:
         res, _ = s.clip_tips(int(k), want_dict=want_dict)
     if pop_bubbles:
         res, _ = s.pop_bubbles(int(k), want_dict=want_dict)
     d = collections.OrderedDict(res.dict_items) if want_dict else None
     return d, res.G(), res.contigs
+
+
+def kmer_spectrum(reads, k=31, limit=1, nbins=1024, session=None):
+    """The k-mer count spectrum of build(reads, k, limit), which the reference does not report:
+    np.uint64[nbins], hist[c] = canonical k-mers of the dict with count c, the last bin holding
+    those with nbins - 1 or more (eulerhip.Session.kmer_spectrum)."""
+    s = _session(session)
+    s.assemble(list(reads), int(k), limit=limit)
+    return s.kmer_spectrum(nbins)
 
 
 def clip_tips(d, k, max_tip_len=None, max_rounds=4, session=None):

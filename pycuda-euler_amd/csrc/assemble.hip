@@ -46,6 +46,7 @@
 #include "join_local.h"
 #include "clip.h"
 #include "pop.h"
+#include "spectrum.h"
 
 #include <atomic>
 #include <chrono>
@@ -364,6 +365,7 @@ struct ec_session {
     DevBuf clip_cand, clip_list, clip_kill, clip_tot;
     // ec_pop_bubbles / ec_copy_contig_kmer_sums (pop.h): branch keys, per-contig sums, the tile table
     DevBuf pop_key, pop_sum, pop_tcnt, pop_toff, pop_tile;
+    DevBuf spec_hist;  // ec_kmer_spectrum (spectrum.h): the global histogram
 };
 
 // ec_clip_tips' refusal after the stepwise calls (ec_session::clip_why)
@@ -4274,7 +4276,7 @@ static void for_each_buf(ec_session *s, Fn fn) {
                      &s->run_cnt, &s->run_ends, &s->run_dends, &s->rt_lb,
                      &s->jl_kof, &s->jl_rs, &s->jl_re, &s->jl_cnt, &s->jl_off, &s->jl_flag, &s->rpack,
                      &s->clip_cand, &s->clip_list, &s->clip_kill, &s->clip_tot,
-                     &s->pop_key, &s->pop_sum, &s->pop_tcnt, &s->pop_toff, &s->pop_tile};
+                     &s->pop_key, &s->pop_sum, &s->pop_tcnt, &s->pop_toff, &s->pop_tile, &s->spec_hist};
     for (auto *b : all) fn(*b);
 }
 
@@ -5480,22 +5482,17 @@ int clip_evaluate(ec_session *s, unsigned int nc, unsigned long long max_len, Cl
     return host_sync(s, st);
 }
 
-// one clipping round: the listed contigs' k-mers marked, the dense arrays exported with the marked
-// records as fillers into recs2 (as ec_assemble_from_kmers holds its records), then the merge and
-// the graph phase of ec_assemble_from_solid on them.  The index is read before the merge rewrites
-// it; recs2 is no scratch of the merge or the graph phase, and nothing else crosses the round.
+// the back half of a round, shared by the clean-ups and ec_refilter: the dense arrays exported with
+// the ids marked in clip_kill as fillers into recs2 (as ec_assemble_from_kmers holds its records),
+// then the merge and the graph phase of ec_assemble_from_solid on them.  recs2 is no scratch of the
+// merge or the graph phase, and nothing else crosses the round.
 template <typename Ops, typename Index>
-int clip_round(ec_session *s, const Index &idx, unsigned int n_clip, unsigned int U) {
+int regraph_round(ec_session *s, unsigned int U) {
     using K = typename Ops::K;
     using Rec = typename RecOf<K>::T;
     hipStream_t st = s->stream;
     const int k = s->k;
-    EC_CHECK(s->clip_kill.ensure(std::max<size_t>(U, 1)));
     EC_CHECK(s->recs2.ensure(std::max<size_t>((size_t)U * sizeof(Rec), 16)));
-    EC_HIP(hipMemsetAsync(s->clip_kill.p, 0, std::max<size_t>(U, 1), st));
-    k_clip_kill<Ops, Index><<<grid_for((uint64_t)n_clip * 64, 256), 256, 0, st>>>(
-        idx, s->clip_list.as<unsigned int>(), n_clip, s->coff.as<unsigned long long>(), s->chars.as<char>(), k, U,
-        s->clip_kill.as<uint8_t>());
     k_clip_export<K><<<grid_for(U, 256), 256, 0, st>>>(s->dkey.as<K>(), s->dcnt.as<unsigned int>(),
                                                        s->dfc.as<unsigned long long>(),
                                                        s->dft.as<unsigned long long>(), s->clip_kill.as<uint8_t>(), U,
@@ -5524,6 +5521,19 @@ int clip_round(ec_session *s, const Index &idx, unsigned int n_clip, unsigned in
     now.n_buckets = was.n_buckets;
     now.record_bytes = was.record_bytes;
     return EC_OK;
+}
+
+// one clipping round: the listed contigs' k-mers marked (the index is read before the merge
+// rewrites it), then the back half
+template <typename Ops, typename Index>
+int clip_round(ec_session *s, const Index &idx, unsigned int n_clip, unsigned int U) {
+    hipStream_t st = s->stream;
+    EC_CHECK(s->clip_kill.ensure(std::max<size_t>(U, 1)));
+    EC_HIP(hipMemsetAsync(s->clip_kill.p, 0, std::max<size_t>(U, 1), st));
+    k_clip_kill<Ops, Index><<<grid_for((uint64_t)n_clip * 64, 256), 256, 0, st>>>(
+        idx, s->clip_list.as<unsigned int>(), n_clip, s->coff.as<unsigned long long>(), s->chars.as<char>(), s->k, U,
+        s->clip_kill.as<uint8_t>());
+    return regraph_round<Ops, Index>(s, U);
 }
 
 // ---- bubble popping, per-contig k-mer count sums (pop.h) ----------------------------------------
@@ -5609,11 +5619,12 @@ int cleanup_loop(ec_session *s, uint32_t max_rounds, Eval eval, uint32_t &rounds
     return EC_OK;
 }
 
-// the refusals ec_clip_tips, ec_pop_bubbles and ec_copy_contig_kmer_sums share
+// the refusals ec_clip_tips, ec_pop_bubbles, ec_copy_contig_kmer_sums, ec_kmer_spectrum and
+// ec_refilter share
 int clip_state_check(ec_session *s, const char *who) {
     if (s->clip_ok) return EC_OK;
     set_error("%s needs the device state of a one-GPU assembly (ec_assemble_*, _from_solid, _from_kmers, "
-              "ec_clip_tips, ec_pop_bubbles): %s", who, s->clip_why);
+              "ec_clip_tips, ec_pop_bubbles, ec_refilter): %s", who, s->clip_why);
     return EC_ERR_STATE;
 }
 
@@ -5669,4 +5680,60 @@ extern "C" int ec_copy_contig_kmer_sums(ec_session *s, uint64_t *sums) {
     EC_CHECK(ksum_any(s, nc, nullptr));
     EC_CHECK(d2h(s, sums, s->pop_sum.p, (size_t)nc * 8, s->stream));
     return host_sync(s, s->stream);
+}
+
+// ---- k-mer count spectrum, re-filter by a new solid limit (spectrum.h) -------------------------
+extern "C" int ec_kmer_spectrum(ec_session *s, uint32_t nbins, uint64_t *hist) {
+    if (nbins < 2 || nbins > EC_SPECTRUM_MAX_BINS) {
+        set_error("ec_kmer_spectrum: nbins %u outside [2, %d]", nbins, EC_SPECTRUM_MAX_BINS);
+        return EC_ERR_ARG;
+    }
+    if (!s || !hist) {
+        set_error("ec_kmer_spectrum: null session / hist");
+        return EC_ERR_ARG;
+    }
+    EC_CHECK(clip_state_check(s, "ec_kmer_spectrum"));
+    std::memset(hist, 0, (size_t)nbins * 8);
+    const unsigned int U = (unsigned int)s->stats.n_solid;
+    if (!U) return EC_OK;
+    EC_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    EC_CHECK(s->spec_hist.ensure((size_t)nbins * 8));
+    EC_HIP(hipMemsetAsync(s->spec_hist.p, 0, (size_t)nbins * 8, st));
+    k_spectrum<<<grid_for((U + 3ull) / 4, 256, 2048), 256, 0, st>>>(s->dcnt.as<unsigned int>(), U, nbins,
+                                                                   s->spec_hist.as<unsigned long long>());
+    EC_HIP(hipGetLastError());
+    EC_CHECK(d2h(s, hist, s->spec_hist.p, (size_t)nbins * 8, st));
+    return host_sync(s, st);
+}
+
+extern "C" int ec_refilter(ec_session *s, uint32_t limit, ec_refilter_info *info) {
+    if (!s || !info) {
+        set_error("ec_refilter: null session / info");
+        return EC_ERR_ARG;
+    }
+    EC_CHECK(clip_state_check(s, "ec_refilter"));
+    *info = ec_refilter_info{};
+    info->limit = limit;
+    EC_HIP(hipSetDevice(s->device));
+    drop_step_state(s);
+    s->dense_ok = false;
+    const unsigned int U = (unsigned int)s->stats.n_solid;
+    if (!U) return EC_OK;
+    hipStream_t st = s->stream;
+    RefilterTotals tot{};
+    EC_CHECK(s->clip_kill.ensure(U));
+    EC_CHECK(s->clip_tot.ensure(sizeof(RefilterTotals)));
+    EC_HIP(hipMemsetAsync(s->clip_tot.p, 0, sizeof(RefilterTotals), st));
+    k_refilter_mark<<<grid_for((U + 3ull) / 4, 256, 2048), 256, 0, st>>>(
+        s->dcnt.as<unsigned int>(), U, limit, s->clip_kill.as<uint8_t>(), s->clip_tot.as<RefilterTotals>());
+    EC_HIP(hipGetLastError());
+    EC_CHECK(d2h(s, &tot, s->clip_tot.p, sizeof(RefilterTotals), st));
+    EC_CHECK(host_sync(s, st));
+    if (!tot.n_removed) return EC_OK;  // (nothing at or below the limit: every result byte stays)
+    if (s->k > 32) EC_CHECK((regraph_round<OpsW, SolidIndexW>(s, U)));
+    else EC_CHECK((regraph_round<Ops64, SolidIndex>(s, U)));
+    info->changed = 1;
+    info->n_removed_kmers = tot.n_removed;
+    return EC_OK;
 }

@@ -84,4 +84,42 @@ bool memlog_on() {
 }  // namespace ec
 
 extern "C" const char *ec_last_error(void) { return ec::g_err; }
-extern "C" int ec_version(void) { return 300; /* 0.3.0: ec_pop_bubbles, ec_copy_contig_kmer_sums */ }
+extern "C" int ec_version(void) { return 400; /* 0.4.0: ec_kmer_spectrum, ec_spectrum_threshold, ec_refilter */ }
+
+// the threshold rule of include/eulerhip.h on a count spectrum: host only, integers only
+extern "C" int ec_spectrum_threshold(const uint64_t *h, uint32_t nbins, ec_spectrum_info *info) {
+    if (nbins < 2 || nbins > EC_SPECTRUM_MAX_BINS) {
+        ec::set_error("ec_spectrum_threshold: nbins %u outside [2, %d]", nbins, EC_SPECTRUM_MAX_BINS);
+        return EC_ERR_ARG;
+    }
+    if (!h || !info) {
+        ec::set_error("ec_spectrum_threshold: null hist / info");
+        return EC_ERR_ARG;
+    }
+    *info = ec_spectrum_info{};
+    uint32_t lo = 0;
+    while (lo < nbins && !h[lo]) lo++;
+    if (lo == nbins) return EC_OK;
+    info->lo = lo;
+    uint32_t d = lo;
+    while (d + 1 < nbins && h[d] >= h[d + 1]) d++;
+    if (d + 1 >= nbins) return EC_OK;  // (never rises)
+    info->descent_end = d;
+    if (d == lo) return EC_OK;
+    uint32_t p = d;
+    for (uint32_t c = d + 1; c < nbins; c++)
+        if (h[c] > h[p]) p = c;
+    info->peak = p;
+    if (p == nbins - 1) return EC_OK;
+    uint64_t m = h[lo];
+    for (uint32_t c = lo; c <= p; c++) m = h[c] < m ? h[c] : m;
+    info->floor = m;
+    uint32_t v = lo;
+    // 16 (h[v] - m) <= h[p] - m, as h[v] - m <= floor((h[p] - m) / 16): no overflow on any input
+    const uint64_t within = (h[p] - m) / EC_SPECTRUM_FLOOR_DIV;
+    while (v < p && h[v] - m > within) v++;
+    if (v == p) return EC_OK;
+    info->found = 1;
+    info->limit = v;
+    return EC_OK;
+}

@@ -19,7 +19,10 @@ Contigs equal referenceAssembler.all_contigs(build(reads, k, limit), k) with rea
 clipped on the device (eulerhip.Session.clip_tips; --tip-len, --tip-rounds) before the outputs
 are written, and the ClipInfo line goes to stderr.  --pop-bubbles (same path) pops bubbles
 (eulerhip.Session.pop_bubbles; --bubble-len, --bubble-rounds), after the tips if both are given,
-and the PopInfo line goes to stderr.
+and the PopInfo line goes to stderr.  --auto-limit (same path) reads the solid limit off the
+assembly's k-mer count spectrum (eulerhip.spectrum_threshold; --spectrum-bins) and re-filters the
+dict by it on the device, before the tips and bubbles; the chosen limit, or that none was found,
+goes to stderr, and --spectrum-out FILE gets the spectrum's non-zero bins as count<TAB>k-mers.
 """
 import argparse
 import os
@@ -58,7 +61,25 @@ def main(argv=None):
     ap.add_argument("--bubble-len", type=int, default=0,
                     help="longest branch popped, in characters (default 2 k; at most 65535)")
     ap.add_argument("--bubble-rounds", type=int, default=4, help="popping rounds at most (default 4)")
+    ap.add_argument("--auto-limit", action="store_true",
+                    help="choose the solid limit from the k-mer count spectrum of the assembly and re-filter by "
+                         "it, before --clip-tips / --pop-bubbles; one process, fused path only")
+    ap.add_argument("--spectrum-bins", type=int, default=1024,
+                    help="bins of the count spectrum, 2 .. 4096 (default 1024; the last bin saturates)")
+    ap.add_argument("--spectrum-out", default="",
+                    help="with --auto-limit: write the spectrum's non-zero bins as count<TAB>k-mers lines")
     a = ap.parse_args(argv)
+    if a.auto_limit and (a.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        # (the spectrum of the sharded path would have to be all-reduced before the solid filter)
+        print("euler_run: --auto-limit works on the one-process fused path only, not with --sharded or "
+              "several ranks", file=sys.stderr)
+        return 2
+    if a.auto_limit and not 2 <= a.spectrum_bins <= 4096:
+        print("euler_run: --spectrum-bins must be in 2 .. 4096", file=sys.stderr)
+        return 2
+    if a.spectrum_out and not a.auto_limit:
+        print("euler_run: --spectrum-out needs --auto-limit", file=sys.stderr)
+        return 2
     if a.clip_tips and (a.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         # (the junction-partitioned graph of the sharded path holds no complete link table)
         print("euler_run: --clip-tips works on the one-process fused path only, not with --sharded or "
@@ -100,6 +121,25 @@ def main(argv=None):
     if not sharded:
         sess = eulerhip.Session(local, stream=torch.cuda.current_stream().cuda_stream)
         sess.run_device(d_buf.data_ptr(), d_off.data_ptr(), hi - lo, a.k, a.limit, 0)
+        res = None
+        if a.auto_limit:
+            st0 = sess.stats()
+            hist = sess.kmer_spectrum(a.spectrum_bins)
+            si = eulerhip.spectrum_threshold(hist)
+            if a.spectrum_out and rank == 0:
+                with open(a.spectrum_out, "w") as f:
+                    f.write("".join("%d\t%d\n" % (c, int(hist[c])) for c in np.flatnonzero(hist)))
+            if si["found"]:
+                res, _ = sess.refilter(a.k, si["limit"])
+                if rank == 0:
+                    print("auto-limit: limit %d  (spectrum lo %d  descent end %d  peak %d  floor %d)  solid k-mers "
+                          "%d -> %d  contigs %d -> %d" % (si["limit"], si["lo"], si["descent_end"], si["peak"],
+                                                          si["floor"], st0.n_solid, res.stats.n_solid, st0.n_contigs,
+                                                          res.stats.n_contigs), file=sys.stderr)
+            elif rank == 0:
+                print("auto-limit: no limit found  (spectrum lo %d  descent end %d  peak %d of %d bins)  solid "
+                      "k-mers %d kept" % (si["lo"], si["descent_end"], si["peak"], a.spectrum_bins, st0.n_solid),
+                      file=sys.stderr)
         if a.clip_tips:
             n0 = sess.stats().n_contigs
             res, ci = sess.clip_tips(a.k, a.tip_len, a.tip_rounds)
@@ -114,7 +154,7 @@ def main(argv=None):
                 print("pop-bubbles: rounds %d  converged %d  bubble contigs %d  bubble k-mers %d  contigs %d -> %d"
                       % (pi["rounds"], pi["converged"], pi["n_bubble_contigs"], pi["n_bubble_kmers"], n0,
                          res.stats.n_contigs), file=sys.stderr)
-        if not a.clip_tips and not a.pop_bubbles:
+        if res is None:
             res = sess.fetch(a.k)
         P = res.stats.n_positions
     else:

@@ -43,6 +43,8 @@ EC_PATH_PARTITIONED = 0
 EC_PATH_GENERAL = 1
 EC_PATH_SUPERKMER = 2
 EC_MAX_K = 63
+EC_SPECTRUM_MAX_BINS = 4096
+EC_SPECTRUM_FLOOR_DIV = 16
 
 
 class EulerHipError(RuntimeError):
@@ -112,6 +114,34 @@ class PopInfo(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class SpectrumInfo(ctypes.Structure):
+    """ec_spectrum_info: what ec_spectrum_threshold read off a count spectrum"""
+    _fields_ = [
+        ("found", ctypes.c_uint32),
+        ("lo", ctypes.c_uint32),
+        ("descent_end", ctypes.c_uint32),
+        ("peak", ctypes.c_uint32),
+        ("limit", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+        ("floor", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "pad"}
+
+
+class RefilterInfo(ctypes.Structure):
+    """ec_refilter_info: what ec_refilter did"""
+    _fields_ = [
+        ("limit", ctypes.c_uint32),
+        ("changed", ctypes.c_uint32),
+        ("n_removed_kmers", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 _lib = None
 
 # exported symbols and their signatures (tests check that every one declared in
@@ -144,6 +174,9 @@ _SIGS = {
     "ec_clip_tips": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ClipInfo)]),
     "ec_pop_bubbles": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(PopInfo)]),
     "ec_copy_contig_kmer_sums": (ctypes.c_int, [_P, _P]),
+    "ec_kmer_spectrum": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
+    "ec_spectrum_threshold": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(SpectrumInfo)]),
+    "ec_refilter": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(RefilterInfo)]),
 }
 
 
@@ -195,6 +228,19 @@ def mem_stats(reset=False):
     h, p = _U64(0), _U64(0)
     check(lib().ec_mem_stats(ctypes.byref(h), ctypes.byref(p), int(bool(reset))))
     return int(h.value), int(p.value)
+
+
+def spectrum_threshold(hist):
+    """The solid limit a k-mer count spectrum suggests (ec_spectrum_threshold; the rule is stated
+    in include/eulerhip.h): hist[c] = k-mers seen c times, the last bin saturating.  Returns
+    {found, lo, descent_end, peak, limit, floor}; found = 0 leaves limit = 0.  Host only: needs
+    neither a session nor a GPU."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if h.ndim != 1:
+        raise ValueError("hist must be one-dimensional")
+    si = SpectrumInfo()
+    check(lib().ec_spectrum_threshold(h.ctypes.data if h.size else None, h.size, ctypes.byref(si)))
+    return si.as_dict()
 
 
 def stage_names():
@@ -455,6 +501,36 @@ class Session:
         out = np.zeros(max(int(self.stats().n_contigs), 1), np.uint64)
         check(lib().ec_copy_contig_kmer_sums(self._h, out.ctypes.data))
         return out[:int(self.stats().n_contigs)]
+
+
+    def kmer_spectrum(self, nbins=1024):
+        """np.uint64[nbins]: the k-mer count spectrum of the session's current dict
+        (ec_kmer_spectrum) -- hist[c] = canonical solid k-mers with dict count c, hist[nbins - 1]
+        those with nbins - 1 or more; changes no state."""
+        nbins = int(nbins)
+        out = np.zeros(max(nbins, 1), np.uint64)
+        check(lib().ec_kmer_spectrum(self._h, nbins & 0xFFFFFFFF, out.ctypes.data))
+        return out
+
+    def refilter(self, k, limit, want_dict=False):
+        """Keep only the k-mers of the session's current dict whose count is > limit and run the
+        graph phase on them (ec_refilter): the results of assemble(limit=limit), without counting
+        the reads again.  Returns (Result, info) with info = {limit, changed, n_removed_kmers};
+        want_dict needs an assembly run with EC_FLAG_WANT_DICT."""
+        ri = RefilterInfo()
+        check(lib().ec_refilter(self._h, int(limit), ctypes.byref(ri)))
+        return self.fetch(k, want_dict), ri.as_dict()
+
+    def auto_limit(self, k, nbins=1024, want_dict=False):
+        """Spectrum -> threshold -> refilter: the solid limit read off the count spectrum of the
+        session's current dict (spectrum_threshold) and applied (refilter).  Returns (Result,
+        spectrum_info, refilter_info); when no threshold is found the results stay as they are
+        and refilter_info is {limit: 0, changed: 0, n_removed_kmers: 0}."""
+        si = spectrum_threshold(self.kmer_spectrum(nbins))
+        if not si["found"]:
+            return self.fetch(k, want_dict), si, RefilterInfo().as_dict()
+        res, ri = self.refilter(k, si["limit"], want_dict)
+        return res, si, ri
 
 
 _default = {}
