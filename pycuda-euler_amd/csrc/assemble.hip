@@ -736,6 +736,8 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
         gsize = ((ntiles + g - 1) / g) * 64;
         G = (nreads + gsize - 1) / gsize;
     }
+    // ((read_base + reads) 2M < 2^32: the events fit 32 bits, and a refined record's position
+    // p = (read_base + read) M + window stays below 2^31 -- its bit 31 carries the flip)
     if (k < SK_MIN_K || k > 32 || M > 256 || gsize * M >= (1ull << 24) || (read_base + nreads) * 2 * M >= (1ull << 32) ||
         kn().no_sk2)
         return EC_OK;
@@ -840,7 +842,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
         k_skrefine<<<dim3((unsigned)C, rs), BUCKET_THREADS, 0, st>>>(recs, s->cnt.as<unsigned int>(), (uint32_t)G, cap,
                                                                       bb, s->recs2.as<uint4>(), fc,
                                                                       s->fcur.as<unsigned long long>(), &dsc->skew, M,
-                                                                      gsize, read_base);
+                                                                      gsize, read_base, k);
         kmark(s, 4, 1);
         unsigned long long *b0 = s->bb2.as<unsigned long long>();
         k_fixed_bounds<<<grid_for(nb, 256), 256, 0, st>>>(s->fcur.as<unsigned long long>(), nb, fc, b0, b0 + nb);
@@ -1005,7 +1007,12 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
             EC_HIP(hipMemsetAsync(s->bmark.p, 0, words * 4, st));
             bm = s->bmark.as<unsigned int>();
         }
-        if (k & 1)
+        if (dbg) {  // (EULERHIP_SK2_STATS: the instantiation with the shader-clock ticks)
+            if (k & 1)
+                k_skbucket3<1024, 1664, NT3, false, true><<<(unsigned)Bk, NT3, 0, st>>>(EC_SKBUCKET_ARGS, dbg, claim_cap, bm);
+            else
+                k_skbucket3<1024, 1664, NT3, true, true><<<(unsigned)Bk, NT3, 0, st>>>(EC_SKBUCKET_ARGS, dbg, claim_cap, bm);
+        } else if (k & 1)
             k_skbucket3<1024, 1664, NT3, false><<<(unsigned)Bk, NT3, 0, st>>>(EC_SKBUCKET_ARGS, dbg, claim_cap, bm);
         else
             k_skbucket3<1024, 1664, NT3, true><<<(unsigned)Bk, NT3, 0, st>>>(EC_SKBUCKET_ARGS, dbg, claim_cap, bm);
@@ -1023,7 +1030,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
         unsigned long long h[16];
         EC_CHECK(d2h(s, h, dbg, 128, st));
         EC_CHECK(host_sync(s, st));
-        const double nw = (double)Bk * (BUCKET_THREADS / 64);  // waves
+        const double nw = (double)Bk * ((plan.slots == 1024 ? 512 : BUCKET_THREADS) / 64);  // waves
         if (skfilt)
             fprintf(stderr, "k_skbucket_filt: %llu buckets: max distinct est %llu, max predicted inserts %llu, max "
                             "seen-twice cells %llu, max records %llu; refused by the predictor %llu, tables filled "

@@ -25,8 +25,15 @@
 //
 // Record (uint4): x, y = bases 0..15, 16..31 (base i at bits 2i), z = bases 32..45 in bits
 // 0..27 | (n - 1) << 28; w = partition: bucket-bits-below-coarse (8) << 24 | p_rel (24 bits,
-// (read - g0) * M + first window); refine output: p = (read_base + read) * M + first window.
-// Events as count_part.h: read = p / M, lf = p % M + o for window o, lr = 2M - 1 - lf.
+// (read - g0) * M + first window).
+// Refined record (k_skrefine's output, what every bucket kernel reads): x, y and the low 28 bits
+// of z = the 2 (n + k - 1) base bits in CANONICAL orientation -- the smaller of the bases masked
+// to their length and their reverse complement, compared z, then y, then x, no flip on a tie --
+// with the bits past the record's length zero, so the words compare and hash as they are; the
+// top 4 bits of z stay n - 1; w = p | flip << 31, p = (read_base + read) * M + first window
+// (p < 2^31: phase_count_sk2 declines unless (read_base + reads) * 2M < 2^32).
+// Events as count_part.h: read = p / M, lf = p % M + o for window o, lr = 2M - 1 - lf; the
+// canonical record's windows by sk2_events (EA + o, EB - o).
 #pragma once
 #include "count_v2.h"
 #include "superkmer.h"
@@ -401,14 +408,58 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
     for (int i = threadIdx.x; i < NREG / 4; i += PT_THREADS) hw[i] = s_hll[i];
 }
 
+// ---- canonical records --------------------------------------------------------------------------
+__device__ inline uint32_t rev2_32b(uint32_t v) {  // superkmer.h rev2_32 with one v_bfrev_b32
+    v = __builtin_bitreverse32(v);
+    return ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
+}
+// Canonical content of a partition record, in place: its L = n + k - 1 bases masked to L (the
+// partition copies bases past the run too) or their reverse complement, whichever is smaller
+// (compared z, then y, then x; no flip on a tie); z keeps (n - 1) << 28.  Returns the flip.
+// Branch-free: selects, no divergent paths.
+__device__ inline bool sk2_canon(uint32_t &r0, uint32_t &r1, uint32_t &r2, int k) {
+    const unsigned int n = (r2 >> 28) + 1, L2 = 2 * (n + (unsigned int)k - 1);  // 2L in [2k, 92]
+    const uint32_t m1 = L2 >= 64 ? 0xFFFFFFFFu : (1u << ((L2 - 32) & 31)) - 1u;  // bits of word 1
+    const uint32_t mw2 = L2 > 64 ? (1u << ((L2 - 64) & 31)) - 1u : 0u;           // bits of word 2
+    const uint32_t x0 = r0, x1 = r1 & m1, x2 = r2 & mw2;
+    // reverse complement of the L bases: rev2 of the 96-bit string (base i -> 47 - i), then
+    // down by 96 - 2L bits (4 .. 54), complemented
+    const uint32_t y0 = rev2_32b(x2), y1 = rev2_32b(x1), y2 = rev2_32b(x0);
+    const unsigned int sft = 96 - L2, s5 = sft & 31;
+    const bool lo = sft < 32;
+    const uint32_t a0 = __builtin_amdgcn_alignbit(y1, y0, s5), a1 = __builtin_amdgcn_alignbit(y2, y1, s5),
+                   a2 = y2 >> s5;
+    const uint32_t q0 = ~(lo ? a0 : a1), q1 = ~(lo ? a1 : a2) & m1, q2 = lo ? ~a2 & mw2 : 0u;
+    const bool flip = q2 != x2 ? q2 < x2 : q1 != x1 ? q1 < x1 : q0 < x0;
+    r0 = flip ? q0 : x0, r1 = flip ? q1 : x1, r2 = (flip ? q2 : x2) | (n - 1) << 28;
+    return flip;
+}
+// Events of a refined record (w = p | flip << 31, n windows): with rd = p / M, rm = p % M,
+// A = rd 2M + rm and B = rd 2M + 2M - 1 - rm, window o of the canonical bases was inserted by
+// build() at EA + o and its twin at EB - o: EA = flip ? B - n + 1 : A, EB = flip ? A + n - 1 : B
+// (window o of the flipped record is the twin of window n - 1 - o as read).
+__device__ inline void sk2_events(uint32_t w, unsigned int n, uint32_t M, double inv_m, uint32_t &EA, uint32_t &EB) {
+    const unsigned int p = w & 0x7FFFFFFFu;
+    const bool flip = (w >> 31) != 0;
+    const unsigned int rd0 = (unsigned int)((double)p * inv_m);  // p / M, corrected below
+    int rm = (int)(p - rd0 * M);
+    unsigned int rd = rd0;
+    if (rm < 0) rd--, rm += (int)M;
+    else if (rm >= (int)M) rd++, rm -= (int)M;
+    const unsigned int A = rd * 2 * M + (unsigned int)rm, B = rd * 2 * M + 2 * M - 1 - (unsigned int)rm;
+    EA = flip ? B - n + 1 : A, EB = flip ? A + n - 1 : B;
+}
+
 // ---- refine: (group, coarse) runs -> fixed-capacity final buckets ------------------------------
 // As k_refine2: workgroup (c, y) reads the runs of groups [G y / RS, G (y + 1) / RS) of coarse
 // bucket c, sorts SK2_TILE-record tiles by final bucket in LDS and appends each final bucket's
 // run at a cursor reserved by one global atomic: final bucket b holds [b fcap, b fcap + fcur[b]).
+// The records leave canonical (sk2_canon; this kernel waits on HBM with its issue slots mostly
+// empty, the bucket kernels behind it are bound by their instruction count).
 __global__ void __launch_bounds__(BUCKET_THREADS) k_skrefine(const uint4 *recs, const unsigned int *cnt, uint32_t G,
                                                              uint64_t cap, int bbits, uint4 *out, uint64_t fcap,
                                                              unsigned long long *fcur, unsigned int *overflow,
-                                                             uint32_t M, uint64_t gsize, uint64_t read_base) {
+                                                             uint32_t M, uint64_t gsize, uint64_t read_base, int k) {
     constexpr int TILE = SK2_TILE;
     constexpr int PER = TILE / BUCKET_THREADS;
     constexpr uint64_t C = 1 << SK2_CBITS;
@@ -467,8 +518,14 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_skrefine(const uint4 *recs, 
             const unsigned int i = threadIdx.x + q * BUCKET_THREADS;
             if (i < n) {
                 jj[q] = fb ? (rw[q] >> 24) >> (SK2_FBITS - fb) : 0u;
-                rw[q] = (uint32_t)((read_base + (uint64_t)(ga + lr[q]) * gsize) * M) + (rw[q] & 0xFFFFFFu);
                 rk[q] = atomicAdd(&tcnt[jj[q]], 1u);
+                // p < 2^31 (phase_count_sk2 declines unless (read_base + reads) 2M < 2^32): bit 31
+                // takes the flip of the canonical bases
+                const uint32_t p = (uint32_t)((read_base + (uint64_t)(ga + lr[q]) * gsize) * M) + (rw[q] & 0xFFFFFFu);
+#ifdef SK2_CHECK_P31  // debug builds (make EXTRA=-DSK2_CHECK_P31): the kernel aborts on a position past 2^31
+                assert((p >> 31) == 0);
+#endif
+                rw[q] = p | (uint32_t)sk2_canon(rx[q], ry[q], rz[q], k) << 31;
             }
         }
         __syncthreads();
@@ -558,11 +615,6 @@ struct EvExpand {  // e -> (read << 32) | l for the dense arrays
 // no barrier is needed -- a record that meets a pending slot of its own key just takes another
 // entry.  Each thread takes RB records per round: their loads, canonical forms and probe chains
 // overlap (one record per thread was bound by the latency of its dependent LDS round trips).
-__device__ inline uint32_t rev2_32b(uint32_t v) {  // superkmer.h rev2_32 with one v_bfrev_b32
-    v = __builtin_bitreverse32(v);
-    return ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
-}
-
 template <int SLOTS, int RS, int RB, bool EVEN_K>
 __global__ void __launch_bounds__(BUCKET_THREADS) k_skbucket(const uint4 *recs, const unsigned long long *bbeg,
                                                              const unsigned long long *bend, int k, uint32_t M,
@@ -609,7 +661,6 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_skbucket(const uint4 *recs, 
     const uint64_t r0 = bbeg[b], r1 = bend[b];
     const uint64_t kmask = kmask64(k);
     const int sh = 2 * (k - 1), fsh = 64 - 2 * k;
-    const unsigned int m2 = 2 * M - 1, M2 = 2 * M;
 
     unsigned long long n_rolled = 0;  // (EULERHIP_SK2_STATS; no global atomics in the loops: they
                                       // would hold the record loads' counter at vmcnt(0))
@@ -711,30 +762,10 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_skbucket(const uint4 *recs, 
             // the records PD rounds on; unconditional (clamped; the value past the end is not
             // used), so the loads stay in order in flight and the wait before use is vmcnt(PD - 1)
             nxd[j] = recs[min(ri + PD * ROUND, r1 - 1)];
-            // canonical content of the record (branch-free: selects, no divergent paths)
-            const unsigned int n = (x.z >> 28) + 1, L2 = 2 * (n + (unsigned int)k - 1);  // 2L in [2k, 92]
-            const uint32_t m1 = L2 >= 64 ? 0xFFFFFFFFu : (1u << ((L2 - 32) & 31)) - 1u;  // bits of word 1
-            const uint32_t mw2 = L2 > 64 ? (1u << ((L2 - 64) & 31)) - 1u : 0u;           // bits of word 2
-            const uint32_t x0 = x.x, x1 = x.y & m1, x2 = x.z & mw2;
-            // reverse complement of the L bases: rev2 of the 96-bit string (base i -> 47 - i), then
-            // down by 96 - 2L bits (4 .. 54), complemented
-            const uint32_t y0 = rev2_32b(x2), y1 = rev2_32b(x1), y2 = rev2_32b(x0);
-            const unsigned int sft = 96 - L2, s5 = sft & 31;
-            const bool lo = sft < 32;
-            const uint32_t a0 = __builtin_amdgcn_alignbit(y1, y0, s5), a1 = __builtin_amdgcn_alignbit(y2, y1, s5),
-                           a2 = y2 >> s5;
-            const uint32_t q0 = ~(lo ? a0 : a1), q1 = ~(lo ? a1 : a2) & m1, q2 = lo ? ~a2 & mw2 : 0u;
-            const bool flip = q2 != x2 ? q2 < x2 : q1 != x1 ? q1 < x1 : q0 < x0;
-            // events of window 0: A = read 2M + first window, B = read 2M + 2M - 1 - first window
-            const unsigned int p = x.w;
-            const unsigned int rd0 = (unsigned int)((double)p * inv_m);  // p / M, corrected below
-            int rm = (int)(p - rd0 * M);
-            unsigned int rd = rd0;
-            if (rm < 0) rd--, rm += (int)M;
-            else if (rm >= (int)M) rd++, rm -= (int)M;
-            const unsigned int A = rd * M2 + (unsigned int)rm, B = rd * M2 + m2 - (unsigned int)rm;
-            K0[j] = flip ? q0 : x0, K1[j] = flip ? q1 : x1, K2[j] = (flip ? q2 : x2) | (n - 1) << 28;
-            EA[j] = flip ? B - n + 1 : A, EB[j] = flip ? A + n - 1 : B;
+            // canonical content and flip as the refine left them; events of window 0
+            const unsigned int n = (x.z >> 28) + 1;
+            K0[j] = x.x, K1[j] = x.y, K2[j] = x.z;
+            sk2_events(x.w, n, M, inv_m, EA[j], EB[j]);
             // content hash -> first slot, tag
             uint32_t hh = K0[j] * 0x9E3779B1u;
             hh = (hh ^ (hh >> 15) ^ K1[j]) * 0x85EBCA77u;
@@ -905,7 +936,9 @@ struct SkB3Lds {
     };
 };
 
-template <int SLOTS, int RS, int NT, bool EVEN_K>
+// STATS (EULERHIP_SK2_STATS): k_skbucket's per-wave shader-clock split of the records phase and
+// the wave-level probe passes in dbg[8..15]; compiled out of the default instantiation.
+template <int SLOTS, int RS, int NT, bool EVEN_K, bool STATS = false>
 __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsigned long long *bbeg,
                                                   const unsigned long long *bend, int k, uint32_t M, double inv_m,
                                                   long long limit, unsigned long long *dkey, unsigned int *dcnt,
@@ -938,7 +971,6 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
     const uint64_t r0 = bbeg[b], r1 = bend[b];
     const uint64_t kmask = kmask64(k);
     const int sh = 2 * (k - 1), fsh = 64 - 2 * k;
-    const unsigned int m2 = 2 * M - 1, M2 = 2 * M;
     unsigned long long n_rolled = 0;
 
     // the n windows of a canonical record into the k-mer table (as k_skbucket's roll_out)
@@ -1004,31 +1036,25 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
 #pragma unroll
     for (int d = 0; d < PD; d++) nx[d] = recs[r1 > r0 ? min(r0 + tid + (uint64_t)d * NT, r1 - 1) : r0];
     auto ld = [](uint32_t *a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+    unsigned long long c_canon = 0, c_probe = 0, c_post = 0, n_iter = 0, n_rounds = 0, c_t = 0;
+    auto tick = [&](unsigned long long &acc) {
+        if constexpr (STATS) {
+            const unsigned long long t = __builtin_amdgcn_s_memtime();
+            acc += t - c_t;
+            c_t = t;
+        }
+    };
+    if constexpr (STATS) c_t = __builtin_amdgcn_s_memtime();
     auto record_round = [&](uint4 &nxd, uint64_t c0) {
+        if constexpr (STATS) n_rounds++;
         const uint64_t ri = c0 + tid;
         const bool valid = ri < r1;
         const uint4 x = nxd;
         nxd = recs[min(ri + PD * NT, r1 - 1)];
-        const unsigned int n = (x.z >> 28) + 1, L2 = 2 * (n + (unsigned int)k - 1);
-        const uint32_t m1 = L2 >= 64 ? 0xFFFFFFFFu : (1u << ((L2 - 32) & 31)) - 1u;
-        const uint32_t mw2 = L2 > 64 ? (1u << ((L2 - 64) & 31)) - 1u : 0u;
-        const uint32_t x0 = x.x, x1 = x.y & m1, x2 = x.z & mw2;
-        const uint32_t y0 = rev2_32b(x2), y1 = rev2_32b(x1), y2 = rev2_32b(x0);
-        const unsigned int sft = 96 - L2, s5 = sft & 31;
-        const bool lo = sft < 32;
-        const uint32_t a0 = __builtin_amdgcn_alignbit(y1, y0, s5), a1 = __builtin_amdgcn_alignbit(y2, y1, s5),
-                       a2 = y2 >> s5;
-        const uint32_t q0 = ~(lo ? a0 : a1), q1 = ~(lo ? a1 : a2) & m1, q2 = lo ? ~a2 & mw2 : 0u;
-        const bool flip = q2 != x2 ? q2 < x2 : q1 != x1 ? q1 < x1 : q0 < x0;
-        const unsigned int p = x.w;
-        const unsigned int rd0 = (unsigned int)((double)p * inv_m);
-        int rm = (int)(p - rd0 * M);
-        unsigned int rd = rd0;
-        if (rm < 0) rd--, rm += (int)M;
-        else if (rm >= (int)M) rd++, rm -= (int)M;
-        const unsigned int A = rd * M2 + (unsigned int)rm, B = rd * M2 + m2 - (unsigned int)rm;
-        const uint32_t K0 = flip ? q0 : x0, K1 = flip ? q1 : x1, K2 = (flip ? q2 : x2) | (n - 1) << 28;
-        const uint32_t EA = flip ? B - n + 1 : A, EB = flip ? A + n - 1 : B;
+        const unsigned int n = (x.z >> 28) + 1;
+        const uint32_t K0 = x.x, K1 = x.y, K2 = x.z;  // canonical as the refine left them
+        uint32_t EA, EB;
+        sk2_events(x.w, n, M, inv_m, EA, EB);
         uint32_t hh = K0 * 0x9E3779B1u;
         hh = (hh ^ (hh >> 15) ^ K1) * 0x85EBCA77u;
         hh = (hh ^ (hh >> 13) ^ K2) * 0xC2B2AE3Du;
@@ -1036,8 +1062,10 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
         const uint32_t TG = (hh | 0x1000u) & 0xFFFFF000u;
         uint32_t SL = __umulhi(hh * 0x27D4EB2Fu, (unsigned int)RS);
         int ST = valid ? 0 : 1;  // 0 searching, 1 found / claimed, 2 past the claim cap
+        tick(c_canon);
 #pragma unroll 1
         while (__any(ST == 0)) {
+            if constexpr (STATS) n_iter++;
             const uint32_t T = ld(&R.tag[SL]);
             asm volatile("" ::: "memory");  // the key words are read after the tag (issue order)
             const uint32_t X = ld(&R.x[SL]), Y = ld(&R.y[SL]), Z = ld(&R.z[SL]);
@@ -1063,6 +1091,7 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
                 }
             }
         }
+        tick(c_probe);
         if (valid && ST == 1) {
             atomicAdd(&R.mult[SL], 1u);
             if (EA < R.a[SL]) atomicMin(&R.a[SL], EA);
@@ -1073,6 +1102,7 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
             if (o < (unsigned int)OV) o_x[o] = K0, o_y[o] = K1, o_z[o] = K2, o_a[o] = EA, o_b[o] = EB;
             else s_over[0] = 1;
         }
+        tick(c_post);
     };
     for (uint64_t c0 = r0; c0 < r1; c0 += PD * NT) {
 #pragma unroll
@@ -1082,6 +1112,14 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
         }
     }
     __syncthreads();
+    if constexpr (STATS) {
+        unsigned long long c_bar = 0;
+        tick(c_bar);
+        if ((tid & 63) == 0) {
+            atomicAdd(&dbg[8], c_canon), atomicAdd(&dbg[9], c_probe), atomicAdd(&dbg[10], c_post);
+            atomicAdd(&dbg[11], n_iter), atomicAdd(&dbg[12], c_bar), atomicAdd(&dbg[13], n_rounds);
+        }
+    }
     // ---- distinct records out of the record table, counted by window count --------------------
     constexpr int PER = (RS + NT - 1) / NT;
     uint32_t cx[PER], cy[PER], cz[PER], cm[PER], ca[PER], cb[PER], bin[PER], rk[PER];
@@ -1124,12 +1162,20 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
         }
     __syncthreads();
     const unsigned int ne = s_ncnt[SK2_NMAX], nov = min(s_nov, (unsigned int)OV);
+    if constexpr (STATS) c_t = __builtin_amdgcn_s_memtime();
     for (unsigned int t = tid; t < ne + nov; t += NT) {
         if (t < ne) roll_out(L.k.x[t], L.k.y[t], L.k.z[t], L.k.mult[t], L.k.a[t], L.k.b[t]);
         else {
             const unsigned int o = t - ne;
             roll_out(o_x[o], o_y[o], o_z[o], 1u, o_a[o], o_b[o]);
         }
+    }
+    if constexpr (STATS) {
+        unsigned long long c_roll = 0, c_bar2 = 0;
+        tick(c_roll);
+        __syncthreads();
+        tick(c_bar2);
+        if ((tid & 63) == 0) atomicAdd(&dbg[14], c_roll), atomicAdd(&dbg[15], c_bar2);
     }
     if (dbg) atomicAdd(&dbg[2], n_rolled);
     lds_table_finish<SLOTS, false, KeyId, LTabE<SLOTS>, EvExpand, NT>(tab, s_over, b, limit, dkey, dcnt, dfc, dft, sub,
@@ -1186,45 +1232,29 @@ __global__ void __launch_bounds__(NT) k_skbucket_filt(const uint4 *recs, const u
     const uint64_t r0 = bbeg[b], r1 = bend[b];
     const uint64_t kmask = kmask64(k);
     const int fsh = 64 - 2 * k;
-    const unsigned int m2 = 2 * M - 1, M2 = 2 * M;
-    // the windows of a record as stored (window o = bases o .. o + k - 1, o < n <= 16): canonical
-    // key, add, first events of the canonical / twin string (k_skbucket3's roll-out, unflipped)
+    // the windows of a record (window o = bases o .. o + k - 1, o < n <= 16): canonical key, add,
+    // first events of the canonical / twin string (k_skbucket3's roll-out)
     auto windows = [&](uint64_t ri, const uint4 &x, auto &&fn) {
         const unsigned int n = (x.z >> 28) + 1;
-        if constexpr (MERGED) {  // canonical record: window o at A + o, its twin at B - o
+        // window o of the canonical bases was inserted at EA + o, its twin at EB - o, mult times:
+        // a merged record brings its event minima and multiplicity, a refined one its position
+        uint32_t EA, EB;
+        unsigned int mult = 1;
+        if constexpr (MERGED) {
             const uint2 e = mev[ri];
-            const unsigned int mult = x.w;
-            for (unsigned int o = 0; o < n; o++) {
-                const uint32_t lo = __builtin_amdgcn_alignbit(x.y, x.x, 2 * o), hi = __builtin_amdgcn_alignbit(x.z, x.y, 2 * o);
-                const uint64_t P = (uint64_t)lo | (uint64_t)hi << 32;
-                const uint64_t rv = ~P & kmask, fw = rev2_64(P) >> fsh;
-                const bool tw = fw > rv;
-                const unsigned int ef = e.x + o, et = e.y - o;
-                unsigned int add = mult, eC = tw ? et : ef, eT = tw ? ef : et;
-                if (EVEN_K && fw == rv) {
-                    add = 2 * mult;
-                    eC = eT = min(ef, et);
-                }
-                fn(tw ? rv : fw, add, eC, eT);
-            }
-            return;
+            EA = e.x, EB = e.y, mult = x.w;
+        } else {
+            sk2_events(x.w, n, M, inv_m, EA, EB);
         }
-        const unsigned int p = x.w;
-        const unsigned int rd0 = (unsigned int)((double)p * inv_m);
-        int rm = (int)(p - rd0 * M);
-        unsigned int rd = rd0;
-        if (rm < 0) rd--, rm += (int)M;
-        else if (rm >= (int)M) rd++, rm -= (int)M;
-        const unsigned int A = rd * M2 + (unsigned int)rm, B = rd * M2 + m2 - (unsigned int)rm;
         for (unsigned int o = 0; o < n; o++) {
             const uint32_t lo = __builtin_amdgcn_alignbit(x.y, x.x, 2 * o), hi = __builtin_amdgcn_alignbit(x.z, x.y, 2 * o);
             const uint64_t P = (uint64_t)lo | (uint64_t)hi << 32;
             const uint64_t rv = ~P & kmask, fw = rev2_64(P) >> fsh;
             const bool tw = fw > rv;
-            const unsigned int ef = A + o, et = B - o;
-            unsigned int add = 1, eC = tw ? et : ef, eT = tw ? ef : et;
+            const unsigned int ef = EA + o, et = EB - o;
+            unsigned int add = mult, eC = tw ? et : ef, eT = tw ? ef : et;
             if (EVEN_K && fw == rv) {
-                add = 2;
+                add = 2 * mult;
                 eC = eT = min(ef, et);
             }
             fn(tw ? rv : fw, add, eC, eT);
@@ -1344,7 +1374,6 @@ __global__ void __launch_bounds__(NT) k_skdedup(const uint4 *recs, const unsigne
     if (tid < (unsigned int)SK2_NMAX) s_ncnt[tid] = 0;
     __syncthreads();
     const uint64_t r0 = bbeg[b], r1 = bend[b];
-    const unsigned int m2 = 2 * M - 1, M2 = 2 * M;
     auto ld = [](uint32_t *a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
     // (the next round's record loaded before this round's probes: one load in flight per
     // thread left the kernel waiting on HBM latency)
@@ -1354,27 +1383,10 @@ __global__ void __launch_bounds__(NT) k_skdedup(const uint4 *recs, const unsigne
         const bool valid = ri < r1;
         const uint4 x = nxt;
         if (c0 + NT < r1) nxt = recs[min(ri + NT, r1 - 1)];
-        // canonical content (k_skbucket3's record round)
-        const unsigned int n = (x.z >> 28) + 1, L2 = 2 * (n + (unsigned int)k - 1);
-        const uint32_t m1 = L2 >= 64 ? 0xFFFFFFFFu : (1u << ((L2 - 32) & 31)) - 1u;
-        const uint32_t mw2 = L2 > 64 ? (1u << ((L2 - 64) & 31)) - 1u : 0u;
-        const uint32_t x0 = x.x, x1 = x.y & m1, x2 = x.z & mw2;
-        const uint32_t y0 = rev2_32b(x2), y1 = rev2_32b(x1), y2 = rev2_32b(x0);
-        const unsigned int sft = 96 - L2, s5 = sft & 31;
-        const bool lo = sft < 32;
-        const uint32_t a0 = __builtin_amdgcn_alignbit(y1, y0, s5), a1 = __builtin_amdgcn_alignbit(y2, y1, s5),
-                       a2 = y2 >> s5;
-        const uint32_t q0 = ~(lo ? a0 : a1), q1 = ~(lo ? a1 : a2) & m1, q2 = lo ? ~a2 & mw2 : 0u;
-        const bool flip = q2 != x2 ? q2 < x2 : q1 != x1 ? q1 < x1 : q0 < x0;
-        const unsigned int p = x.w;
-        const unsigned int rd0 = (unsigned int)((double)p * inv_m);
-        int rm = (int)(p - rd0 * M);
-        unsigned int rd = rd0;
-        if (rm < 0) rd--, rm += (int)M;
-        else if (rm >= (int)M) rd++, rm -= (int)M;
-        const unsigned int A = rd * M2 + (unsigned int)rm, B = rd * M2 + m2 - (unsigned int)rm;
-        const uint32_t K0 = flip ? q0 : x0, K1 = flip ? q1 : x1, K2 = (flip ? q2 : x2) | (n - 1) << 28;
-        const uint32_t EA = flip ? B - n + 1 : A, EB = flip ? A + n - 1 : B;
+        const unsigned int n = (x.z >> 28) + 1;
+        const uint32_t K0 = x.x, K1 = x.y, K2 = x.z;  // canonical as the refine left them
+        uint32_t EA, EB;
+        sk2_events(x.w, n, M, inv_m, EA, EB);
         uint32_t hh = K0 * 0x9E3779B1u;
         hh = (hh ^ (hh >> 15) ^ K1) * 0x85EBCA77u;
         hh = (hh ^ (hh >> 13) ^ K2) * 0xC2B2AE3Du;
