@@ -187,6 +187,14 @@ int ec_pack_reads(const uint8_t *reads, const uint64_t *offsets, uint64_t nreads
                   uint64_t *exc_pos, uint8_t *exc_byte, uint64_t exc_cap, uint64_t *n_exc, uint32_t *read_len);
 
 int ec_get_stats(ec_session *s, ec_stats *out);
+/* Speculative launches of the session since it was created (kernels queued on the previous call's
+ * shape while the host waits for a count): out[0] / out[1] = the graph phase's
+ * first link kernels queued behind the solid count's read-back and kept / queued and run again
+ * (the count was redone, the solid count outgrew the assumed capacity, the tables changed);
+ * out[2] / out[3] = the same for the contig starts' read-back (no launch is queued on it by this
+ * version: both stay 0).  The results never depend on them.  EULERHIP_DEBUG=1 EULERHIP_NO_SPEC=1
+ * queues none. */
+int ec_spec_counts(ec_session *s, uint64_t out[4]);
 const char *ec_stage_name(int stage);
 /* contigs: chars[n_contig_chars], offsets[n_contigs+1] (all_contigs r, in order) */
 int ec_copy_contigs(ec_session *s, char *chars, uint64_t *offsets);

@@ -224,6 +224,21 @@ struct ec_session {
         uint32_t M = 0;
         int k = 0, bbits = 0;
     } skspec;
+    // links_local's first two kernels (k_jl_init, k_jl_scan) queued by phase_count_sk2 behind its
+    // bucket kernel, on the previous call's shape, while the host waits for the solid count: the
+    // scan reads U from the device and stops at ucap.  valid: links_local's shape of the previous
+    // call; queued: this call's prologue is in the stream and the count has not been redone since.
+    // Odd k only (even k needs k_upal between the two; left unspeculated)
+    struct JlSpec {
+        bool valid = false, queued = false;
+        int bits = 0, k = 0;
+        unsigned int ucap = 0, fcap = 0;
+    } jlspec;
+    DevBuf jl_frec;  // the prologue's foreign records (s->recs still feeds a second refine)
+    bool graph_follows = false;  // the call goes on to phase_graph (assemble): the prologue may run
+    // ec_spec_counts: prologues kept / run again behind the solid count's read-back [0], [1]; the
+    // same for the contig starts' read-back [2], [3], on which nothing is queued
+    uint64_t spec_cnt[4] = {0, 0, 0, 0};
     PinnedVec<uint64_t> h_coff;  // result readbacks land in pinned host memory
     PinnedVec<uint64_t> h_loff;
     PinnedVec<int64_t> h_links;
@@ -233,6 +248,9 @@ struct ec_session {
     PinnedVec<uint8_t> h_lc8;
     PinnedVec<uint32_t> h_links32;
     bool links_compact = false;
+    // few contigs (k_links_small): link total, emission flag, contig offsets, links and link counts
+    // as one block (in dcounts on the device), copied once and taken apart on the host
+    HostBuf h_blk;
     bool want_dict = false;
     hipEvent_t ev[2 * EC_NSTAGES] = {};
     hipEvent_t kev[2 * EC_NKERNELS] = {};
@@ -483,6 +501,32 @@ struct Scalars {  // device scalars block
     unsigned long long chains;       // k_tile_compact: the tile contraction's chain count
     unsigned int active[64];
 };
+static_assert(sizeof(Scalars) % 8 == 0 && offsetof(Scalars, bad) % 8 == 0, "k_scal_reset writes 64-bit words");
+
+// the scalars as a call finds them, in one launch (two fills before): all zero, bad = ~0
+__global__ void __launch_bounds__(64) k_scal_reset(Scalars *sc) {
+    unsigned long long *w = reinterpret_cast<unsigned long long *>(sc);
+    for (unsigned int i = threadIdx.x; i < sizeof(Scalars) / 8; i += 64)
+        w[i] = i == offsetof(Scalars, bad) / 8 ? ~0ull : 0ull;
+}
+
+// the emission's three node maps set to NONE and its flag word cleared in one launch (four fills
+// were four); n = nodes a map
+__global__ void __launch_bounds__(256) k_emit_init(unsigned int *a, unsigned int *b, unsigned int *c, uint64_t n,
+                                                   unsigned int *flag) {
+    const uint64_t t0 = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, st = (uint64_t)gridDim.x * blockDim.x;
+    if (t0 == 0) *flag = 0;
+    // (hipMalloc'd buffers: 16-byte aligned; the tail by single words)
+    const uint64_t n4 = n / 4;
+    const uint4 v = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    uint4 *a4 = reinterpret_cast<uint4 *>(a), *b4 = reinterpret_cast<uint4 *>(b), *c4 = reinterpret_cast<uint4 *>(c);
+    for (uint64_t i = t0; i < n4; i += st) {
+        a4[i] = v;
+        b4[i] = v;
+        c4[i] = v;
+    }
+    for (uint64_t i = 4 * n4 + t0; i < n; i += st) a[i] = b[i] = c[i] = 0xFFFFFFFFu;
+}
 
 int scan_u64(ec_session *s, const unsigned long long *in, unsigned long long *out, size_t n) {
     size_t bytes = 0;
@@ -607,9 +651,9 @@ int begin_call(ec_session *s, int k, unsigned flags) {
     for (auto &u : s->kused) u = false;
     for (auto &u : s->sused) u = false;
     EC_CHECK(s->scal.ensure(sizeof(Scalars)));
-    Scalars *dsc = s->scal.as<Scalars>();
-    EC_HIP(hipMemsetAsync(dsc, 0, sizeof(Scalars), s->stream));
-    EC_HIP(hipMemsetAsync(&dsc->bad, 0xFF, sizeof(unsigned long long), s->stream));
+    s->jlspec.queued = false;
+    s->graph_follows = false;
+    k_scal_reset<<<1, 64, 0, s->stream>>>(s->scal.as<Scalars>());
     return EC_OK;
 }
 
@@ -768,7 +812,9 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
     uint4 *recs = s->recs.as<uint4>();
     const uint32_t smask = P >= (1ull << 26) ? 255u : 0u;
     unsigned int *hreg = s->ftot.as<unsigned int>();
-    EC_HIP(hipMemsetAsync(&dsc->nrec, 0, sizeof(unsigned long long), st));
+    // (validate: the call's first kernel -- the scalars are as begin_call, or reset() after an
+    // invalid first try, left them; only k_skpart_w writes nrec)
+    if (!validate) EC_HIP(hipMemsetAsync(&dsc->nrec, 0, sizeof(unsigned long long), st));
     mark(s, 2 * EC_STAGE_COUNT);
     kmark(s, 1, 0);
 #define EC_SKPART_WV(NPF, W, VAL)                                                                             \
@@ -904,7 +950,8 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
     const uint64_t Bk = 1ull << bbits;
     const uint64_t NR = hsc.nrec;
     uint64_t fcap = NR * 2 / Bk + 1024;
-    if (spec && sp.bbits == bbits && sp.fcap >= fcap && sp.fcap <= fcap + fcap / 8) {
+    const bool refine_stood = spec && sp.bbits == bbits && sp.fcap >= fcap && sp.fcap <= fcap + fcap / 8;
+    if (refine_stood) {
         fcap = sp.fcap;  // the speculative refine stands
     } else {
         if (spec && verbose) fprintf(stderr, "count_sk2: refine plan changed (bits %d -> %d), refined again\n", sp.bbits, bbits);
@@ -1002,7 +1049,8 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
         const unsigned int claim_cap = kn().sk2_claim > 0 ? (unsigned int)kn().sk2_claim : ~0u;
         unsigned int *bm = nullptr;
         if (kn().tile_plan != 0) {  // (bucket starts for the tile ranking: one bit per dense id)
-            const size_t words = umax / 32 + 2;
+            // (a whole number of 256-B lines: the runtime fills an odd tail in a second launch)
+            const size_t words = (umax / 32 + 2 + 63) & ~size_t(63);
             EC_CHECK(s->bmark.ensure(words * 4));
             EC_HIP(hipMemsetAsync(s->bmark.p, 0, words * 4, st));
             bm = s->bmark.as<unsigned int>();
@@ -1052,7 +1100,49 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
     kmark(s, 2, 1);
     mark(s, 2 * EC_STAGE_COMPACT + 1);
     EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
-    EC_CHECK(host_sync(s, st));
+    // The graph phase's first kernels behind the bucket kernel while the host waits for the solid
+    // count (a ~26 us hole on the headline: wake-up, plan, allocations' checks, first launch):
+    // links_local's k_jl_init and k_jl_scan on the previous call's shape, the scan reading U from
+    // the device.  Only where the speculative refine stood (a stream of like batches) on a call
+    // that goes on to phase_graph; links_local takes them over if the count stood (no overflow,
+    // no second refine) and U fits, and runs its own otherwise.  They write nothing the count's
+    // redo paths read: the foreign records go to jl_frec, not to s->recs (the second refine's input)
+    const auto jp = s->jlspec;
+    s->jlspec.queued = false;
+    if (!attempt && refine_stood && jp.valid && s->graph_follows && !s->no_index && !skfilt && !dbg &&
+        (k & 1) && jp.k == k && jp.bits == bbits && kn().jl_bits_delta == 0 && kn().jl_fcap <= 0 &&
+        kn().join_links != 0 && kn().join_local != 0) {
+        const unsigned int ntab = 1u << jp.bits;
+        EC_CHECK(s->jl_kof.ensure((size_t)jp.ucap * 4));
+        EC_CHECK(s->jl_rs.ensure((size_t)ntab * 4));
+        EC_CHECK(s->jl_re.ensure((size_t)ntab * 4));
+        EC_CHECK(s->jl_cnt.ensure(((size_t)ntab + 1) * 4));
+        EC_CHECK(s->jl_off.ensure(((size_t)ntab + 1) * 4));
+        EC_CHECK(s->jl_flag.ensure((size_t)(JL_NCTR + 1) * JL_CSTRIDE * 4));
+        EC_CHECK(s->jl_frec.ensure((size_t)jp.fcap * sizeof(RecJ64)));
+        EC_CHECK(s->upal.ensure(jp.ucap));
+        EC_CHECK(s->succ.ensure((size_t)jp.ucap * 8));
+        if (!s->rd_ev) EC_HIP(hipEventCreateWithFlags(&s->rd_ev, hipEventDisableTiming));
+        EC_HIP(hipEventRecord(s->rd_ev, st));
+        unsigned int *flags = s->jl_flag.as<unsigned int>();
+        k_jl_init<<<grid_for(2ull * jp.ucap, 256, 4096), 256, 0, st>>>(
+            flags, (JL_NCTR + 1) * JL_CSTRIDE, s->jl_rs.as<unsigned int>(), s->jl_cnt.as<unsigned int>(), ntab,
+            s->succ.as<unsigned int>(), 2ull * jp.ucap, s->upal.as<uint8_t>(), jp.ucap);
+        k_jl_scan<unsigned long long><<<grid_for(jp.ucap, 256, 8192), 256, 0, st>>>(
+            s->dkey.as<unsigned long long>(), jp.ucap, k, jp.bits, s->upal.as<uint8_t>(), s->jl_kof.as<unsigned int>(),
+            s->jl_frec.as<RecJ64>(), flags + JL_CSTRIDE, jp.fcap, s->jl_cnt.as<unsigned int>(),
+            s->jl_rs.as<unsigned int>(), s->jl_re.as<unsigned int>(), &flags[1], &dsc->nsolid, &flags[2]);
+        EC_CHECK(host_wait(s, s->rd_ev));
+        // (the scan held U to ucap: a larger count, like an overflow, leaves the prologue unused;
+        // phase_graph counts a prologue links_local did not take over as redone)
+        s->jlspec.queued = true;
+        if (hsc.skew || hsc.overflow || hsc.nsolid > jp.ucap) {
+            s->jlspec.queued = false;
+            s->spec_cnt[1]++;
+        }
+    } else {
+        EC_CHECK(host_sync(s, st));
+    }
     if (!hsc.skew || attempt) break;
     // a final bucket past fcap: a repeat family's minimizers (copies x coverage records each) on an
     // input whose buckets hold a few thousand records.  k_skrefine's cursors counted every record,
@@ -2603,21 +2693,34 @@ int links_local(ec_session *s, int k, unsigned int U, const Index &sidx, bool &o
     Scalars *dsc = s->scal.as<Scalars>();
     const uint64_t N = 2ull * U;
     // foreign records: ~2 / (w + 1) of the 2U (7 % at k = 31, 3 % at k = 51); room for a third
-    const unsigned int fcap = kn().jl_fcap > 0 ? ((unsigned int)kn().jl_fcap / JL_NCTR + 1) * JL_NCTR
-                                               : (U / 3 / JL_NCTR + 64) * JL_NCTR;
+    auto fcap_of = [](unsigned int u) { return (u / 3 / JL_NCTR + 64) * JL_NCTR; };
+    unsigned int fcap = kn().jl_fcap > 0 ? ((unsigned int)kn().jl_fcap / JL_NCTR + 1) * JL_NCTR : fcap_of(U);
+    // phase_count_sk2's prologue (k_jl_init, k_jl_scan on the previous call's shape) stands when it
+    // assumed this call's tables and its capacities hold U: its foreign records, in regions of its
+    // own (larger) capacity, are in jl_frec
+    const auto jp = s->jlspec;
+    const bool pro = jp.queued && std::is_same<K, unsigned long long>::value && jp.bits == bits && jp.k == k &&
+                     U <= jp.ucap && jp.fcap >= fcap && kn().jl_fcap <= 0;
+    s->jlspec = ec_session::JlSpec{};
+    if (jp.queued && !pro) s->spec_cnt[1]++;  // (redone below)
+    if (pro) fcap = jp.fcap;
     EC_CHECK(s->jl_kof.ensure((size_t)U * 4));
     EC_CHECK(s->jl_rs.ensure((size_t)ntab * 4));
     EC_CHECK(s->jl_re.ensure((size_t)ntab * 4));
     EC_CHECK(s->jl_cnt.ensure(((size_t)ntab + 1) * 4));
     EC_CHECK(s->jl_off.ensure(((size_t)ntab + 1) * 4));
     EC_CHECK(s->jl_flag.ensure((size_t)(JL_NCTR + 1) * JL_CSTRIDE * 4));
-    EC_CHECK(s->recs.ensure((size_t)fcap * sizeof(R)));
+    if (!pro) EC_CHECK(s->recs.ensure((size_t)fcap * sizeof(R)));
     EC_CHECK(s->recs2.ensure((size_t)fcap * sizeof(R)));
-    // [1]: the gate; [JL_CSTRIDE (r + 1)]: foreign records of region r
+    // [1]: the gate; [2]: the prologue's U past its capacity; [JL_CSTRIDE (r + 1)]: foreign records of region r
     unsigned int *flags = s->jl_flag.as<unsigned int>(), *fctr = flags + JL_CSTRIDE;
     unsigned int *cnt = s->jl_cnt.as<unsigned int>(), *off = s->jl_off.as<unsigned int>();
     const K *dkey = s->dkey.as<K>();
     uint8_t *upal = s->upal.as<uint8_t>();
+    const R *frec = pro ? s->jl_frec.as<R>() : s->recs.as<R>();
+    if (pro) {
+        s->spec_cnt[0]++;
+    } else {
     // (odd k: no palindromic k-mer, the flags a fill in the same launch; even k: k_upal)
     k_jl_init<<<grid_for(N, B, 4096), B, 0, st>>>(flags, (JL_NCTR + 1) * JL_CSTRIDE, s->jl_rs.as<unsigned int>(), cnt,
                                                  ntab, s->succ.as<unsigned int>(), N, (k & 1) ? upal : nullptr, U);
@@ -2625,10 +2728,11 @@ int links_local(ec_session *s, int k, unsigned int U, const Index &sidx, bool &o
     k_jl_scan<K><<<grid_for(U, B, 8192), B, 0, st>>>(dkey, U, k, bits, upal, s->jl_kof.as<unsigned int>(), s->recs.as<R>(),
                                                      fctr, fcap, cnt, s->jl_rs.as<unsigned int>(),
                                                      s->jl_re.as<unsigned int>(), &flags[1]);
+    }
     k_jl_edges<<<grid_for(U / 64 + 2, B, 4096), B, 0, st>>>(s->jl_kof.as<unsigned int>(), U, s->jl_rs.as<unsigned int>(),
                                                            s->jl_re.as<unsigned int>(), &flags[1]);
     EC_CHECK(scan_excl_u32(s, cnt, off, (size_t)ntab + 1));
-    k_jl_scatter<R><<<grid_for(fcap, B, 4096), B, 0, st>>>(s->recs.as<R>(), fctr, fcap, off, cnt, s->recs2.as<R>());
+    k_jl_scatter<R><<<grid_for(fcap, B, 4096), B, 0, st>>>(frec, fctr, fcap, off, cnt, s->recs2.as<R>());
     // (4096 slots: 96 KB of 128-bit slots, one workgroup a CU -- 512 threads to hide the probes)
 #define EC_JL_JOIN(SL, ODD)                                                                                        \
     k_jl_join<K, SL, SL / 8, ODD><<<ntab, SL / 8, 0, st>>>(dkey, s->jl_kof.as<unsigned int>(), s->jl_rs.as<unsigned int>(), \
@@ -2645,6 +2749,15 @@ int links_local(ec_session *s, int k, unsigned int U, const Index &sidx, bool &o
     EC_HIP(hipGetLastError());
     gate = &flags[1];
     ok = true;
+    // what the next call's prologue may assume: these tables, and room for a sixteenth more keys
+    // (batches of a stream differ a little; its init and scan pay for the room they do not use)
+    if (std::is_same<K, unsigned long long>::value && kn().no_spec == 0) {
+        s->jlspec.valid = true;
+        s->jlspec.bits = bits;
+        s->jlspec.k = k;
+        s->jlspec.ucap = (unsigned int)std::min<uint64_t>((uint64_t)U + U / 16 + 64, (uint64_t)CYC / 2 - 1);
+        s->jlspec.fcap = fcap_of(s->jlspec.ucap);
+    }
     return EC_OK;
 }
 
@@ -2913,14 +3026,22 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
     // links by the half-edge join (join_w.h) instead of neighbour probes from ~2e6 keys on, for
     // every index (measured on the headline's minimizer index, round 4: links 0.34 ms joined
     // against 0.50 ms probed, EULERHIP_JOIN_LINKS=0)
-    bool joined = false;
+    bool joined = false, local = false;
     const unsigned int *gate = nullptr;
     constexpr bool XT = std::is_same<Ops, OpsX>::value;  // extended alphabet (extended.h)
     if constexpr (!XT) {
         // inside the count's minimizer tables first (join_local.h), when the ids are grouped so
         if (U && !ext_succ && kn().join_links != 0 && kn().join_local != 0 &&
-            (kn().join_local == 1 || kn().join_links == 1 || U >= (1u << 21)))
+            (kn().join_local == 1 || kn().join_links == 1 || U >= (1u << 21))) {
             EC_CHECK(links_local<Ops>(s, k, U, sidx, joined, gate));
+            local = joined;
+        }
+    }
+    // (a prologue phase_count_sk2 queued and links_local did not take over: redone, or not needed;
+    // without a local join this call, the next call has no shape to assume)
+    if (s->jlspec.queued) s->spec_cnt[1]++;
+    if (!local || s->jlspec.queued) s->jlspec = ec_session::JlSpec{};
+    if constexpr (!XT) {
         if (!joined && U && !ext_succ && k >= 8 && kn().join_links != 0 && (kn().join_links == 1 || U >= (1u << 21)))
         {
             if constexpr (std::is_same<Index, SolidIndexW>::value) {
@@ -3133,16 +3254,12 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
     EC_CHECK(s->svals.ensure(Nn * 4));
     EC_CHECK(s->skeys2.ensure(Nn * 8));
     EC_CHECK(s->svals2.ensure(Nn * 4));
-    // the emission's node maps, cleared before the starts' read-back (the device works through
-    // them while the host waits)
+    // the emission's node maps are cleared behind the starts' read-back copy (below): the device
+    // works through the fills while the host wakes up; the start kernels read none of them
     EC_CHECK(s->headOf.ensure(Nn * 4));
     EC_CHECK(s->tailOf.ensure(Nn * 4));
-    EC_HIP(hipMemsetAsync(s->headOf.p, 0xFF, Nn * 4, st));
-    EC_HIP(hipMemsetAsync(s->tailOf.p, 0xFF, Nn * 4, st));
-    EC_HIP(hipMemsetAsync(&dsc->skew, 0, 4, st));  // k_emit: a position past the character bound
     unsigned long long async_M64 = 0;
     auto starts_pass = [&]() -> int {
-    EC_HIP(hipMemsetAsync(s->cidxOf.p, 0xFF, Nn * 4, st));
     if (U)
     {
         const unsigned int nblk = (unsigned int)((N + RULER_CHUNK - 1) / RULER_CHUNK);
@@ -3162,7 +3279,12 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
                                            &dsc->nstarts);
     }
     EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));  // nstarts, active[], the chain count
-    EC_CHECK(host_sync(s, st));
+    if (!s->rd_ev) EC_HIP(hipEventCreateWithFlags(&s->rd_ev, hipEventDisableTiming));
+    EC_HIP(hipEventRecord(s->rd_ev, st));
+    // (skew: k_emit raises it at a position past the character bound)
+    k_emit_init<<<grid_for(Nn / 4 + 1, B, 2048), B, 0, st>>>(s->headOf.as<unsigned int>(), s->tailOf.as<unsigned int>(),
+                                                            s->cidxOf.as<unsigned int>(), Nn, &dsc->skew);
+    EC_CHECK(host_wait(s, s->rd_ev));
     async_M64 = hsc.chains;
     return EC_OK;
     };
@@ -3253,8 +3375,9 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
     // the total travels with the other results (no round trip here): the character buffer is
     // sized for the bound 2U + nc (k - 1) (a walk covers at most its path; a self-twin path's
     // nodes are up to twice its canonical k-mers)
+    // (few contigs: k_links_small's result block carries the offsets and the total)
     EC_CHECK(s->h_coff.resize(nc + 1));
-    EC_CHECK(d2h(s, &s->h_coff[nc], s->coff.as<unsigned long long>() + nc, 8, st));
+    if (!small) EC_CHECK(d2h(s, &s->h_coff[nc], s->coff.as<unsigned long long>() + nc, 8, st));
     // the results' copies to host memory run on the output stream, each as soon as its data is
     // final: the contig offsets here (overlapping emission and GFA), the characters after the
     // emission, the link offsets after the GFA counts (ecoli10m_err: 1.1 M contigs, 47 MB of
@@ -3358,21 +3481,26 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
     s->links_compact = true;
     EC_CHECK(s->h_lc8.resize(n2));
     if (!nc) s->h_coff[0] = 0;
-    if (nc && !ocopy) EC_CHECK(d2h(s, s->h_coff.data(), s->coff.p, (size_t)nc * 8, st));
+    if (nc && !ocopy && !small) EC_CHECK(d2h(s, s->h_coff.data(), s->coff.p, (size_t)nc * 8, st));
     unsigned long long nlinks64 = 0;
+    unsigned int emit_bad = 0;
+    // the small path's result block: [link total u64][emission flag u32, pad][contig offsets
+    // (nc + 1) u64][links 8 n2 u32 (their bound)][link counts n2 bytes]
+    const size_t blk_coff = 16, blk_links = blk_coff + ((size_t)nc + 1) * 8, blk_lc8 = blk_links + (size_t)n2 * 8 * 4,
+                 blk_bytes = blk_lc8 + n2;
     if (nc && small) {
         // (n2 <= 8192: counts, offsets and the compacted links in one launch; the links' bound
-        // 8 n2 travels with the total, so no second round trip follows)
-        EC_CHECK(s->lc8.ensure(n2));
-        EC_CHECK(s->dcounts.ensure((size_t)n2 * 8 * 4));
-        EC_CHECK(s->skeys2.ensure(8));
-        k_links_small<<<1, SMALL_LINK_NT, 0, st>>>(s->lk.as<long long>(), s->lcnt.as<unsigned int>(), n2,
-                                                   s->lc8.as<uint8_t>(), s->dcounts.as<uint32_t>(),
-                                                   s->skeys2.as<unsigned long long>());
-        EC_CHECK(d2h(s, s->h_lc8.data(), s->lc8.p, n2, st));
-        EC_CHECK(s->h_links32.resize((size_t)n2 * 8));
-        EC_CHECK(d2h(s, s->h_links32.data(), s->dcounts.p, (size_t)n2 * 8 * 4, st));
-        EC_CHECK(d2h(s, &nlinks64, s->skeys2.p, 8, st));
+        // 8 n2 travels with the total, so no second round trip follows -- and with them the contig
+        // offsets and the emission's flag: one copy where six 4-5 us copies stood in a row)
+        EC_CHECK(s->dcounts.ensure(blk_bytes));
+        EC_CHECK(s->h_blk.resize(blk_bytes));
+        char *blk = s->dcounts.as<char>();
+        k_links_small<<<1, SMALL_LINK_NT, 0, st>>>(
+            s->lk.as<long long>(), s->lcnt.as<unsigned int>(), n2, reinterpret_cast<uint8_t *>(blk + blk_lc8),
+            reinterpret_cast<uint32_t *>(blk + blk_links), reinterpret_cast<unsigned long long *>(blk),
+            s->coff.as<unsigned long long>(), nc + 1, reinterpret_cast<unsigned long long *>(blk + blk_coff),
+            &dsc->skew, reinterpret_cast<unsigned int *>(blk + 8));
+        EC_CHECK(d2h(s, s->h_blk.data(), blk, blk_bytes, st));
     } else if (nc) {
         EC_CHECK(s->skeys.ensure(((size_t)n2 + 1) * 8));   // per-side counts as u64 (starts sorted)
         EC_CHECK(s->skeys2.ensure(((size_t)n2 + 1) * 8));  // their exclusive scan = link offsets
@@ -3390,9 +3518,18 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
         EC_CHECK(scan_u64(s, s->skeys.as<unsigned long long>(), s->skeys2.as<unsigned long long>(), (size_t)n2 + 1));
         EC_CHECK(d2h(s, &nlinks64, s->skeys2.as<unsigned long long>() + n2, 8, st));
     }
-    unsigned int emit_bad = 0;
-    EC_CHECK(d2h(s, &emit_bad, &dsc->skew, 4, st));
+    if (!(nc && small)) EC_CHECK(d2h(s, &emit_bad, &dsc->skew, 4, st));
     EC_CHECK(host_sync(s, st));  // h_coff[nc] (the characters), the link total
+    if (nc && small) {
+        const char *hb = s->h_blk.data();
+        std::memcpy(&nlinks64, hb, 8);
+        std::memcpy(&emit_bad, hb + 8, 4);
+        std::memcpy(s->h_coff.data(), hb + blk_coff, ((size_t)nc + 1) * 8);
+        std::memcpy(s->h_lc8.data(), hb + blk_lc8, n2);
+        nlinks64 = std::min<unsigned long long>(nlinks64, (unsigned long long)n2 * 8);
+        EC_CHECK(s->h_links32.resize(nlinks64));
+        std::memcpy(s->h_links32.data(), hb + blk_links, (size_t)nlinks64 * 4);
+    }
     const uint64_t nchars = s->h_coff[nc];
     if (emit_bad || nchars > chars_bound) EC_HIP(hipStreamSynchronize(s->ostream));  // (no copy left in flight)
     if (emit_bad) {
@@ -4084,6 +4221,7 @@ int assemble(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, uint6
         return phase_graph<OpsW>(s, k, U, sidx);
     }
     SolidIndex sidx{};
+    s->graph_follows = true;  // (phase_graph<Ops64> below: phase_count_sk2 may queue links_local's prologue)
     const int rc = phase_count(s, d_reads, d_off, nreads, 0, k, (long long)limit, flags, U, sidx);
     if (rc == EC_ERR_ALPHABET) {  // bytes other than A/C/G/T/N: opaque symbols (extended.h)
         EC_CHECK(pipe_all(s));
@@ -4281,7 +4419,7 @@ static void for_each_buf(ec_session *s, Fn fn) {
                      &s->jrec, &s->joid, &s->jout, &s->jseg, &s->jcnt, &s->xrec,
                      &s->skm_rec, &s->skm_ev, &s->skm_end, &s->wcodes_tab,
                      &s->run_cnt, &s->run_ends, &s->run_dends, &s->rt_lb,
-                     &s->jl_kof, &s->jl_rs, &s->jl_re, &s->jl_cnt, &s->jl_off, &s->jl_flag, &s->rpack,
+                     &s->jl_kof, &s->jl_rs, &s->jl_re, &s->jl_cnt, &s->jl_off, &s->jl_flag, &s->jl_frec, &s->rpack,
                      &s->clip_cand, &s->clip_list, &s->clip_kill, &s->clip_tot,
                      &s->pop_key, &s->pop_sum, &s->pop_tcnt, &s->pop_toff, &s->pop_tile, &s->spec_hist};
     for (auto *b : all) fn(*b);
@@ -4360,6 +4498,7 @@ int ec_session_trim(ec_session *s, uint64_t min_bytes) {
     s->bmark_ok = false;
     s->seg_marks = 0;
     s->skspec.valid = false;
+    s->jlspec.valid = s->jlspec.queued = false;  // (its capacities are those of released buffers)
     s->graph_loaded = false;
     s->placed = false;
     s->pipe.active = false;
@@ -4392,6 +4531,7 @@ int ec_session_destroy(ec_session *s) {
     s->h_links.release();
     s->h_lc8.release();
     s->h_links32.release();
+    s->h_blk.release();
     if (s->events) {
         for (auto &e : s->ev) hipEventDestroy(e);
         for (auto &e : s->kev) hipEventDestroy(e);
@@ -4546,6 +4686,12 @@ int ec_get_stats(ec_session *s, ec_stats *out) {
         return EC_ERR_STATE;
     }
     *out = s->stats;
+    return EC_OK;
+}
+
+int ec_spec_counts(ec_session *s, uint64_t out[4]) {
+    if (!s || !out) return EC_ERR_ARG;
+    for (int i = 0; i < 4; i++) out[i] = s->spec_cnt[i];
     return EC_OK;
 }
 

@@ -34,7 +34,8 @@ struct Knobs {
     int rank_sync = 0;          // EULERHIP_RANK_SYNC=1: tile ranking with host-read counts (A/B)
     int rj_div = 0;             // EULERHIP_RJ_DIV: rank_supers_async's Wyllie grids cover N / RJ_DIV rulers (A/B)
     int tile_plan = -1;         // EULERHIP_TILE_PLAN=0: fixed rank tiles, not cut at bucket starts (A/B)
-    int no_spec = 0;            // EULERHIP_NO_SPEC=1: no speculative refine launch (count_sk2, A/B)
+    int no_spec = 0;            // EULERHIP_NO_SPEC=1: no speculative launch (count_sk2's refine, the links' prologue
+                                // behind the solid count, the early character copy; A/B)
     bool merge_mix = false;     // EULERHIP_MERGE_MIX: key-hash buckets / owners instead of minimizers
     int skf_merge = 1;          // EULERHIP_SKF_MERGE: error-rich records merged before the filter (0 off, 2 2560-entry tables)
     bool merge_decode = false;  // EULERHIP_MERGE_DECODE: the owner merge reads a decoded copy of the received records

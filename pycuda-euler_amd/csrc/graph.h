@@ -1006,13 +1006,21 @@ __global__ void __launch_bounds__(256) k_links_compact(const long long *lk, cons
 
 // Few contigs (k_starts_small's bound, n2 = 2 nc <= 8192 sides): the per-side link counts as
 // bytes, their offsets and the compacted links in one workgroup, the total to *nlinks -- the
-// count, scan and compaction launches with the host round trip between them in one launch
+// count, scan and compaction launches with the host round trip between them in one launch.
+// The step's last kernel: it also gathers the other small results next to its own (the contig
+// offsets coff[0 .. ncoff) to coff_out, the emission's flag *bad to *bad_out), so that one
+// contiguous block travels to the host in one copy instead of six
 constexpr unsigned int SMALL_LINK_NT = 1024;
 __global__ void __launch_bounds__(SMALL_LINK_NT) k_links_small(const long long *lk, const unsigned int *lcnt,
                                                               unsigned int n2, uint8_t *c8, uint32_t *out,
-                                                              unsigned long long *nlinks) {
+                                                              unsigned long long *nlinks,
+                                                              const unsigned long long *coff, unsigned int ncoff,
+                                                              unsigned long long *coff_out, const unsigned int *bad,
+                                                              unsigned int *bad_out) {
     __shared__ unsigned int s_sum[SMALL_LINK_NT];
     const unsigned int tid = threadIdx.x;
+    for (unsigned int i = tid; i < ncoff; i += SMALL_LINK_NT) coff_out[i] = coff[i];
+    if (tid == 0) *bad_out = *bad;
     unsigned int c[8], run = 0;
 #pragma unroll
     for (int u = 0; u < 8; u++) {

@@ -103,14 +103,26 @@ constexpr unsigned int JL_NCTR = 256, JL_CSTRIDE = 32;
 // shuffles (rs / re; a table met twice opens the gate); the pairs across wave edges are left to
 // k_jl_edges.  (No private arrays: the candidate records stay in named registers -- a
 // runtime-indexed array put them in scratch, 0.83 ms at the headline.)
+// dU non-null (the launch queued before the host knows the solid count, phase_count_sk2): U is
+// read from it and held to U, the capacity of kof and of the arrays k_jl_init prepared; a count
+// past it raises *over, and the host, which checks the same, runs init and scan again.
 template <typename K>
 __global__ void __launch_bounds__(256) k_jl_scan(const K *dkey, unsigned int U, int k, int bits, const uint8_t *upal,
                                                  unsigned int *kof, typename JLRec<K>::R *fout,
                                                  unsigned int *fcount, unsigned int fcap, unsigned int *fcnt,
-                                                 unsigned int *rs, unsigned int *re, unsigned int *gate) {
+                                                 unsigned int *rs, unsigned int *re, unsigned int *gate,
+                                                 const unsigned int *dU = nullptr, unsigned int *over = nullptr) {
     using R = typename JLRec<K>::R;
     const int j = k - 1, lane = threadIdx.x & 63;
     const K mj = kmask_j(j, (K *)nullptr);
+    if (dU) {
+        const unsigned int u = *dU;
+        if (u > U) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) *over = 1u;
+        } else {
+            U = u;
+        }
+    }
     for (uint64_t t0 = (uint64_t)blockIdx.x * 256; t0 < U; t0 += (uint64_t)gridDim.x * 256) {
         const uint64_t u = t0 + threadIdx.x;
         const bool valid = u < U;

@@ -167,6 +167,7 @@ _SIGS = {
                                      ctypes.POINTER(ctypes.c_uint32)]),
     "ec_assemble_from_kmers": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _U64, ctypes.c_int, ctypes.c_uint]),
     "ec_get_stats": (ctypes.c_int, [_P, ctypes.POINTER(Stats)]),
+    "ec_spec_counts": (ctypes.c_int, [_P, ctypes.POINTER(_U64 * 4)]),
     "ec_stage_name": (ctypes.c_char_p, [ctypes.c_int]),
     "ec_copy_contigs": (ctypes.c_int, [_P, _P, _P]),
     "ec_copy_links": (ctypes.c_int, [_P, _P, _P]),
@@ -427,6 +428,13 @@ class Session:
         st = Stats()
         check(lib().ec_get_stats(self._h, ctypes.byref(st)))
         return st
+
+    def spec_counts(self):
+        """Speculative launches of this session so far (ec_spec_counts): {"links_taken",
+        "links_redone", "starts_taken", "starts_redone"}."""
+        out = (_U64 * 4)()
+        check(lib().ec_spec_counts(self._h, ctypes.byref(out)))
+        return dict(zip(("links_taken", "links_redone", "starts_taken", "starts_redone"), (int(x) for x in out)))
 
     def fetch(self, k, want_dict=False):
         st = self.stats()
