@@ -508,6 +508,10 @@ int ec_count_shard(ec_session *s, const uint8_t *d_reads, const uint64_t *d_offs
  *   - ec_export_by_owner* / ec_export_dense need the records of the last ec_count_shard /
  *     ec_merge_owned*: EC_ERR_STATE after anything else in the list above, after ec_graph_place
  *     (which moves them) and on a new session;
+ *   - ec_dense_spectrum / ec_dense_refilter need the same records and are refused the same way;
+ *     ec_dense_refilter keeps that state (the records that remain are held as the merge would have
+ *     left them) and drops what was derived from the removed ones: the owner ids of a counts-only
+ *     ec_export_by_owner and any pending step records;
  *   - ec_graph_links_part / ec_graph_finish need a set loaded by ec_graph_load that no later
  *     call replaced (ec_graph_place included: a placed segment has no index): EC_ERR_ARG;
  *   - ec_graph_join / ec_graph_links_apply need a segment placed by ec_graph_place: EC_ERR_ARG;
@@ -547,6 +551,28 @@ int ec_session_set_owner_rule(ec_session *s, int rule);
 int ec_merge_owned(ec_session *s, const void *d_records, uint64_t n, int k, int limit, unsigned flags);
 /* copy the held records to d_out (after ec_count_shard with global first events, as the export) */
 int ec_export_dense(ec_session *s, void *d_out);
+/* The solid limit chosen after the owner merge (csrc/dense_filter.h) -- ec_kmer_spectrum and
+ * ec_refilter for the sharded flow, where a rank holds its owner segment and no assembly.
+ *
+ * ec_dense_spectrum: hist[nbins], 2 <= nbins <= EC_SPECTRUM_MAX_BINS: hist[c] = held records whose
+ * count is c (c < nbins-1); hist[nbins-1] = those with count >= nbins-1; sum(hist) ==
+ * ec_dense_count.  Owners are disjoint, so after ec_merge_owned* the job's spectrum is the
+ * element-wise sum of the ranks' histograms, and ec_spectrum_threshold on that sum gives every
+ * rank the same limit.  After ec_count_shard the counts are the shard's own (a k-mer seen in two
+ * shards is two records with partial counts): those histograms are NOT additive across shards.
+ * Valid exactly where ec_export_dense is; EC_ERR_STATE otherwise, before the device is touched;
+ * EC_ERR_ARG for a NULL session or hist or nbins out of range.  Changes no state.
+ *
+ * ec_dense_refilter: every held record with count <= limit is removed from the session's dense
+ * arrays, the order of the rest unchanged, without a second merge or recount.  Afterwards
+ * ec_dense_count, ec_export_dense, ec_export_by_owner*, ec_graph_place and ec_get_stats' n_solid
+ * see the filtered set: as a set of records, what ec_merge_owned* with that limit would have left.
+ * n_removed_kmers counts records; changed = 1 iff at least one was removed.  If no record has
+ * count <= limit (any limit at or below the merge's own included) no held byte changes and
+ * changed = 0; a "low" limit is no error.  Removing every record leaves ec_dense_count == 0.
+ * Valid and refused as ec_dense_spectrum (EC_ERR_ARG for a NULL session or info). */
+int ec_dense_spectrum(ec_session *s, uint32_t nbins, uint64_t *hist);
+int ec_dense_refilter(ec_session *s, uint32_t limit, ec_refilter_info *info);
 /* ec_merge_owned + ec_export_dense in one call (no host round trip between them); d_out holds
  * up to n records, ec_dense_count gives how many were written */
 int ec_merge_owned_export(ec_session *s, const void *d_records, uint64_t n, int k, int limit, unsigned flags,

@@ -47,6 +47,7 @@
 #include "clip.h"
 #include "pop.h"
 #include "spectrum.h"
+#include "dense_filter.h"
 
 #include <atomic>
 #include <chrono>
@@ -5886,6 +5887,99 @@ extern "C" int ec_refilter(ec_session *s, uint32_t limit, ec_refilter_info *info
     if (!tot.n_removed) return EC_OK;  // (nothing at or below the limit: every result byte stays)
     if (s->k > 32) EC_CHECK((regraph_round<OpsW, SolidIndexW>(s, U)));
     else EC_CHECK((regraph_round<Ops64, SolidIndex>(s, U)));
+    info->changed = 1;
+    info->n_removed_kmers = tot.n_removed;
+    return EC_OK;
+}
+
+// ---- the same on the held dense records of the sharded path (dense_filter.h) --------------------
+static int dense_state_check(ec_session *s, const char *who) {
+    if (s->dense_ok) return EC_OK;
+    set_error("%s: no counted or merged records (ec_count_shard / ec_merge_owned*), or a later call replaced them", who);
+    return EC_ERR_STATE;
+}
+
+extern "C" int ec_dense_spectrum(ec_session *s, uint32_t nbins, uint64_t *hist) {
+    if (nbins < 2 || nbins > EC_SPECTRUM_MAX_BINS) {
+        set_error("ec_dense_spectrum: nbins %u outside [2, %d]", nbins, EC_SPECTRUM_MAX_BINS);
+        return EC_ERR_ARG;
+    }
+    if (!s || !hist) {
+        set_error("ec_dense_spectrum: null session / hist");
+        return EC_ERR_ARG;
+    }
+    EC_CHECK(dense_state_check(s, "ec_dense_spectrum"));
+    std::memset(hist, 0, (size_t)nbins * 8);
+    const unsigned int n = s->n_dense;
+    if (!n) return EC_OK;
+    EC_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    EC_CHECK(s->spec_hist.ensure((size_t)nbins * 8));
+    EC_HIP(hipMemsetAsync(s->spec_hist.p, 0, (size_t)nbins * 8, st));
+    k_spectrum<<<grid_for((n + 3ull) / 4, 256, 2048), 256, 0, st>>>(s->dcnt.as<unsigned int>(), n, nbins,
+                                                                   s->spec_hist.as<unsigned long long>());
+    EC_HIP(hipGetLastError());
+    EC_CHECK(d2h(s, hist, s->spec_hist.p, (size_t)nbins * 8, st));
+    return host_sync(s, st);
+}
+
+template <typename K>
+static int dense_compact(ec_session *s, unsigned int n, unsigned int kept, unsigned int nblk, unsigned int limit) {
+    hipStream_t st = s->stream;
+    // (scratch first: a failed allocation leaves the held records as they are)
+    EC_CHECK(s->recs.ensure((size_t)n * sizeof(K)));
+    EC_CHECK(s->midx.ensure((size_t)n * 4));
+    EC_CHECK(s->recs2.ensure((size_t)n * 16));
+    unsigned int *bc = s->rbc.as<unsigned int>(), *bs = bc + nblk;
+    unsigned long long *ofc = s->recs2.as<unsigned long long>(), *oft = ofc + n;
+    EC_CHECK(scan_incl_u32(s, bc, bs, nblk));
+    k_dense_write<K><<<nblk, 256, 0, st>>>(s->dkey.as<K>(), s->dcnt.as<unsigned int>(), s->dfc.as<unsigned long long>(),
+                                          s->dft.as<unsigned long long>(), n, limit, bs, s->recs.as<K>(),
+                                          s->midx.as<unsigned int>(), ofc, oft);
+    EC_HIP(hipGetLastError());
+    if (kept) {
+        EC_HIP(hipMemcpyAsync(s->dkey.p, s->recs.p, (size_t)kept * sizeof(K), hipMemcpyDeviceToDevice, st));
+        EC_HIP(hipMemcpyAsync(s->dcnt.p, s->midx.p, (size_t)kept * 4, hipMemcpyDeviceToDevice, st));
+        EC_HIP(hipMemcpyAsync(s->dfc.p, ofc, (size_t)kept * 8, hipMemcpyDeviceToDevice, st));
+        EC_HIP(hipMemcpyAsync(s->dft.p, oft, (size_t)kept * 8, hipMemcpyDeviceToDevice, st));
+    }
+    return EC_OK;
+}
+
+extern "C" int ec_dense_refilter(ec_session *s, uint32_t limit, ec_refilter_info *info) {
+    if (!s || !info) {
+        set_error("ec_dense_refilter: null session / info");
+        return EC_ERR_ARG;
+    }
+    EC_CHECK(dense_state_check(s, "ec_dense_refilter"));
+    *info = ec_refilter_info{};
+    info->limit = limit;
+    const unsigned int n = s->n_dense;
+    if (!n) return EC_OK;
+    EC_HIP(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    const unsigned int nblk = (unsigned int)((n + (uint64_t)DF_SPAN - 1) / DF_SPAN);
+    RefilterTotals tot{};
+    EC_CHECK(s->rbc.ensure((size_t)nblk * 8));
+    EC_CHECK(s->clip_tot.ensure(sizeof(RefilterTotals)));
+    EC_HIP(hipMemsetAsync(s->clip_tot.p, 0, sizeof(RefilterTotals), st));
+    k_dense_count<<<nblk, 256, 0, st>>>(s->dcnt.as<unsigned int>(), n, limit, s->rbc.as<unsigned int>(),
+                                        s->clip_tot.as<RefilterTotals>());
+    EC_HIP(hipGetLastError());
+    EC_CHECK(d2h(s, &tot, s->clip_tot.p, sizeof(RefilterTotals), st));
+    EC_CHECK(host_sync(s, st));
+    if (!tot.n_removed) return EC_OK;  // (nothing at or below the limit: every held byte stays)
+    const unsigned int kept = n - (unsigned int)tot.n_removed;
+    if (s->k > 32) EC_CHECK(dense_compact<K128>(s, n, kept, nblk, limit));
+    else EC_CHECK(dense_compact<unsigned long long>(s, n, kept, nblk, limit));
+    // what was derived from the old set: pending step records, the cached owner ids of a counts-only
+    // ec_export_by_owner, the merge's bucket marks (they cut the old ids)
+    drop_step_state(s);
+    s->own_valid = false;
+    s->bmark_ok = false;
+    s->seg_marks = 0;
+    s->n_dense = kept;
+    s->stats.n_solid = kept;
     info->changed = 1;
     info->n_removed_kmers = tot.n_removed;
     return EC_OK;

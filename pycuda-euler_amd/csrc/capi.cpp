@@ -84,7 +84,7 @@ bool memlog_on() {
 }  // namespace ec
 
 extern "C" const char *ec_last_error(void) { return ec::g_err; }
-extern "C" int ec_version(void) { return 400; /* 0.4.0: ec_kmer_spectrum, ec_spectrum_threshold, ec_refilter */ }
+extern "C" int ec_version(void) { return 500; /* 0.5.0: ec_dense_spectrum, ec_dense_refilter */ }
 
 // the threshold rule of include/eulerhip.h on a count spectrum: host only, integers only
 extern "C" int ec_spectrum_threshold(const uint64_t *h, uint32_t nbins, ec_spectrum_info *info) {

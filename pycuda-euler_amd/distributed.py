@@ -87,6 +87,7 @@ def owner_rule_for(totals, k):
     return OWNER_HASH if mean > 0 and max(totals) > SKEW * mean else OWNER_MINIMIZER
 eulerhip.register("ec_merge_owned", ctypes.c_int, [_P, _P, _U64, ctypes.c_int, ctypes.c_int, ctypes.c_uint])
 eulerhip.register("ec_export_dense", ctypes.c_int, [_P, _P])
+# (ec_dense_spectrum / ec_dense_refilter, the solid limit chosen after the owner merge: eulerhip._SIGS)
 eulerhip.register("ec_assemble_from_solid", ctypes.c_int, [_P, _P, _U64, ctypes.c_int, ctypes.c_uint])
 eulerhip.register("ec_record_bytes", ctypes.c_int, [ctypes.c_int])
 eulerhip.register("ec_graph_load", ctypes.c_int, [_P, _P, _U64, ctypes.c_int, ctypes.c_uint])
@@ -268,6 +269,30 @@ class HipEngine:
         eulerhip.check(self.L.ec_merge_owned_export(self._h(), ctypes.c_void_p(recs.data_ptr()), n, int(k),
                                                     int(limit), flags, ctypes.c_void_p(out.data_ptr())))
         m = int(self.L.ec_dense_count(self._h()))
+        return out[: m * rb]
+
+    # the solid limit chosen after the owner merge: ec_dense_spectrum / ec_dense_refilter
+    def dense_spectrum(self, nbins=1024):
+        """np.uint64[nbins]: the count spectrum of the held records (ec_dense_spectrum); after an
+        owner merge the ranks' histograms sum to the job's spectrum"""
+        nbins = int(nbins)
+        out = np.zeros(max(nbins, 1), np.uint64)
+        eulerhip.check(self.L.ec_dense_spectrum(self._h(), nbins & 0xFFFFFFFF, out.ctypes.data))
+        return out
+
+    def dense_refilter(self, limit):
+        """drop the held records with count <= limit, order kept (ec_dense_refilter); returns
+        (records kept, {limit, changed, n_removed_kmers})"""
+        ri = eulerhip.RefilterInfo()
+        eulerhip.check(self.L.ec_dense_refilter(self._h(), int(limit), ctypes.byref(ri)))
+        return int(self.L.ec_dense_count(self._h())), ri.as_dict()
+
+    def export_dense(self):
+        """the held records as exchange records (ec_export_dense), a device tensor"""
+        m = int(self.L.ec_dense_count(self._h()))
+        rb = self.rec_bytes()
+        out = self.empty(m * rb)
+        eulerhip.check(self.L.ec_export_dense(self._h(), ctypes.c_void_p(out.data_ptr())))
         return out[: m * rb]
 
     def assemble_from_solid(self, recs, k, flags=0, fetch=True):
@@ -586,8 +611,53 @@ def finish_mode(finish, k, rule):
     return "partitioned" if minimizer_owners(k) and rule == OWNER_MINIMIZER else "replicated"
 
 
+AUTO_METHODS = ("dense_spectrum", "dense_refilter", "export_dense")
+
+
+def check_auto_engine(engine):
+    """auto_limit needs the engine's dense_spectrum / dense_refilter / export_dense"""
+    missing = [m for m in AUTO_METHODS if not hasattr(engine, m)]
+    if missing:
+        raise RuntimeError("auto_limit: engine %s has no %s" % (type(engine).__name__, " / ".join(missing)))
+
+
+def choose_limit(hist, auto_info=None):
+    """eulerhip.spectrum_threshold on the job's summed spectrum (every rank holds the same
+    histogram, so every rank gets the same answer).  auto_info, a dict, receives the threshold's
+    fields, "spectrum" = {count: k-mers} of the non-zero bins, and the job's solid k-mers
+    "n_solid_before" / "n_solid_after" the limit (read off the histogram: a found limit lies
+    below the peak, which lies below the saturating bin)."""
+    hist = np.asarray(hist, dtype=np.uint64)
+    si = eulerhip.spectrum_threshold(hist)
+    if auto_info is not None:
+        before = int(hist.sum())
+        auto_info.update(si)
+        auto_info["spectrum"] = {int(c): int(hist[c]) for c in np.flatnonzero(hist)}
+        auto_info["n_solid_before"] = before
+        auto_info["n_solid_after"] = before - (int(hist[: si["limit"] + 1].sum()) if si["found"] else 0)
+    return si
+
+
+def auto_refilter(engine, comm, ur, spectrum_bins=1024, auto_info=None):
+    """The solid limit chosen after the owner merge: this rank's spectrum of its owner segment
+    (owners are disjoint: the segments' spectra sum to the job's), one all-reduce, the threshold
+    rule, and -- if it finds a limit -- the segment re-filtered in place.  Returns the records
+    this rank holds afterwards (ur when no limit was found)."""
+    hist = comm.allreduce_vec(engine.dense_spectrum(spectrum_bins))
+    si = choose_limit(hist, auto_info)
+    return engine.dense_refilter(si["limit"])[0] if si["found"] else ur
+
+
+def local_auto_refilter(engines, urs, spectrum_bins=1024, auto_info=None):
+    """auto_refilter for simulated ranks: the all-reduce is a plain sum over the engines"""
+    hist = np.sum([eng.dense_spectrum(spectrum_bins) for eng in engines], axis=0, dtype=np.uint64)
+    si = choose_limit(hist, auto_info)
+    return [eng.dense_refilter(si["limit"])[0] for eng in engines] if si["found"] else list(urs)
+
+
 def sharded_assemble(engine, comm, d_reads, d_off, nreads, read_base, k, limit=1, flags=0, on_count=None,
-                     phase_ms=None, partitioned=None, fetch=True, finish="auto"):
+                     phase_ms=None, partitioned=None, fetch=True, finish="auto", auto_limit=False,
+                     spectrum_bins=1024, auto_info=None):
     """Run steps 1-4 for this rank; returns (result, n_positions_total).  on_count(stats)
     receives the shard-count statistics (per-kernel times with EC_FLAG_TIMING); phase_ms, a
     dict, receives the wall time of every step (device-synchronised by the engine calls).
@@ -599,9 +669,16 @@ def sharded_assemble(engine, comm, d_reads, d_off, nreads, read_base, k, limit=1
     ranks / emits its own segment and ONLY RANK 0 returns the result (None on the others);
     "replicated": the successor parts are all-gathered and every rank returns the result.  An
     engine without graph_place runs the replicated finish for "partitioned" too (with a
-    RuntimeWarning), and then every rank returns the result."""
+    RuntimeWarning), and then every rank returns the result.
+    auto_limit: the owner merge runs at `limit`, then the job's k-mer count spectrum (the ranks'
+    ec_dense_spectrum, all-reduced) chooses the solid limit (eulerhip.spectrum_threshold) and every
+    rank re-filters its segment by it in place (ec_dense_refilter) before the graph: the result
+    of limit = the chosen one, without a second merge.  No limit found: the merge's stays.
+    spectrum_bins: the spectrum's bins; auto_info, a dict: see choose_limit."""
     import time
 
+    if auto_limit:
+        check_auto_engine(engine)
     if partitioned is None:
         partitioned = hasattr(engine, "graph_load") and not (flags & eulerhip.EC_FLAG_GENERAL)
     marks = [("start", time.perf_counter())]
@@ -647,14 +724,24 @@ def sharded_assemble(engine, comm, d_reads, d_off, nreads, read_base, k, limit=1
         ur = engine.merge_owned_from(received, src_bytes, src_base, src_lfb, k, limit, flags, export=False)
         del received
         tick("merge")
+        if auto_limit:
+            ur = auto_refilter(engine, comm, ur, spectrum_bins, auto_info)
+            tick("auto_limit")
         lo, hi, _, npal = junction_links(engine, comm, k, ur, tick=tick)
         res = partitioned_finish(engine, comm, k, lo, hi, None, fetch=fetch, tick=tick, npal=npal)
         if phase_ms is not None:
             for (_, a), (name, b) in zip(marks, marks[1:]):
                 phase_ms[name] = phase_ms.get(name, 0.0) + (b - a) * 1e3
         return res, P
-    solid = engine.merge_owned_from(received, src_bytes, src_base, src_lfb, k, limit, flags)
-    tick("merge")
+    if auto_limit:
+        ur = engine.merge_owned_from(received, src_bytes, src_base, src_lfb, k, limit, flags, export=False)
+        tick("merge")
+        auto_refilter(engine, comm, ur, spectrum_bins, auto_info)
+        solid = engine.export_dense()
+        tick("auto_limit")
+    else:
+        solid = engine.merge_owned_from(received, src_bytes, src_base, src_lfb, k, limit, flags)
+        tick("merge")
     if not partitioned:
         everything = comm.allgatherv(solid, fill=0xFF)  # filler records: all-ones keys, skipped
         tick("allgather")
@@ -697,10 +784,12 @@ class ShardedAssembler:
     """bench.py / CLI front-end: this rank's shard of a read set already in host memory is
     moved to its GPU once; run() performs one full distributed assembly."""
 
-    def __init__(self, buf, off, k, limit, rank, world, local_rank, comm=None, read_base=None):
+    def __init__(self, buf, off, k, limit, rank, world, local_rank, comm=None, read_base=None, auto_limit=False,
+                 spectrum_bins=1024, auto_info=None):
         """read_base None: (buf, off) is the whole read set and this rank takes its contiguous
         shard; otherwise (buf, off) is this rank's shard already, its first read being global
-        read read_base (the ranks' shards in rank order form the job's read set)."""
+        read read_base (the ranks' shards in rank order form the job's read set).  auto_limit,
+        spectrum_bins, auto_info: as sharded_assemble."""
         import torch
 
         if read_base is None:
@@ -711,6 +800,7 @@ class ShardedAssembler:
         self.nreads = hi - lo
         self.read_base = lo if read_base is None else int(read_base)
         self.k, self.limit = k, limit
+        self.auto_limit, self.spectrum_bins, self.auto_info = auto_limit, spectrum_bins, auto_info
         self.d_reads = torch.from_numpy(np.ascontiguousarray(buf[b0:b1])).to(f"cuda:{local_rank}")
         self.d_off = torch.from_numpy((off[lo:hi + 1] - off[lo]).astype(np.int64)).to(f"cuda:{local_rank}")
         torch.cuda.synchronize()
@@ -725,7 +815,9 @@ class ShardedAssembler:
         flags = eulerhip.EC_FLAG_TIMING if timing is True else int(timing or 0)
         self.result, self.total_positions = sharded_assemble(self.engine, self.comm, self.d_reads, self.d_off,
                                                              self.nreads, self.read_base, self.k, self.limit, flags,
-                                                             on_count=self._keep, phase_ms=self.phase_ms, fetch=fetch)
+                                                             on_count=self._keep, phase_ms=self.phase_ms, fetch=fetch,
+                                                             auto_limit=self.auto_limit,
+                                                             spectrum_bins=self.spectrum_bins, auto_info=self.auto_info)
         return self.result
 
     def _keep(self, st):
@@ -737,7 +829,7 @@ class ShardedAssembler:
 
 
 def streaming_assemble(engine, buf, off, k, limit=1, chunk_reads=4_000_000, fold=4, read_base=0, flags=0,
-                       stats=None):
+                       stats=None, auto_limit=False, spectrum_bins=1024, auto_info=None):
     """Out-of-core count on one GPU for read sets whose one-shot count does not fit its memory
     (BASELINE config 5 on fewer than 8 GPUs, larger genomes; the reference's chunk loop,
     src/eulercuda.py:99-119, never finished).  The reads (host arrays: buf, uint64 offsets) go
@@ -749,8 +841,13 @@ def streaming_assemble(engine, buf, off, k, limit=1, chunk_reads=4_000_000, fold
     the one rank of the partitioned flow.  Events are global read ids from read_base, so the
     dict order, contigs and links equal the one-shot assembly's (tests: bit-exact vs the oracle
     at forced small chunks).  stats (a dict): chunks, folds, device-buffer peak, positions.
+    auto_limit: after the last merge (at `limit`) the merged set's spectrum chooses the solid limit
+    and the set is re-filtered in place, as in sharded_assemble (one rank: nothing to reduce).
     Returns (result, k-mer positions)."""
     import torch
+
+    if auto_limit:
+        check_auto_engine(engine)
 
     dev = engine.device
     nreads = len(off) - 1
@@ -787,6 +884,8 @@ def streaming_assemble(engine, buf, off, k, limit=1, chunk_reads=4_000_000, fold
             nfold += 1
             engine.sess.trim(64 << 20)
     ur = merge(([running] if running else []) + pending, limit, False)
+    if auto_limit:
+        ur = local_auto_refilter([engine], [ur], spectrum_bins, auto_info)[0]
     running = None
     pending = []
     jrecs, _, npal = engine.graph_place(0, ur, 1)
@@ -800,9 +899,11 @@ def streaming_assemble(engine, buf, off, k, limit=1, chunk_reads=4_000_000, fold
     return res, P
 
 
-def local_sharded_assemble(engines, buf, off, k, limit=1, flags=0, partitioned=None, finish="auto", compact=True):
+def local_sharded_assemble(engines, buf, off, k, limit=1, flags=0, partitioned=None, finish="auto", compact=True,
+                           auto_limit=False, spectrum_bins=1024, auto_info=None):
     """Simulate the distributed algorithm with len(engines) ranks on the local device(s):
-    same engine calls, the collectives done by concatenation.  Returns rank 0's result."""
+    same engine calls, the collectives done by concatenation.  Returns rank 0's result.
+    auto_limit, spectrum_bins, auto_info: as sharded_assemble (the histograms summed here)."""
     world = len(engines)
     nreads = len(off) - 1
     parts = []
@@ -810,15 +911,20 @@ def local_sharded_assemble(engines, buf, off, k, limit=1, flags=0, partitioned=N
         lo, hi = shard_range(nreads, r, world)
         b0, b1 = int(off[lo]), int(off[hi])
         parts.append((buf[b0:b1], off[lo:hi + 1] - off[lo], lo))
-    return local_sharded_assemble_shards(engines, parts, k, limit, flags, partitioned, finish, compact)
+    return local_sharded_assemble_shards(engines, parts, k, limit, flags, partitioned, finish, compact,
+                                         auto_limit=auto_limit, spectrum_bins=spectrum_bins, auto_info=auto_info)
 
 
-def local_sharded_assemble_shards(engines, parts, k, limit=1, flags=0, partitioned=None, finish="auto", compact=True):
+def local_sharded_assemble_shards(engines, parts, k, limit=1, flags=0, partitioned=None, finish="auto", compact=True,
+                                  auto_limit=False, spectrum_bins=1024, auto_info=None):
     """local_sharded_assemble on given shards: parts[r] = (buf, off, read_base) of rank r (host
     arrays; global read ids read_base.., increasing with r, gaps allowed).  compact: the
     exchange's record format per rank (a bool for all; compact records where events fit)."""
     import torch
 
+    if auto_limit:
+        for eng in engines:
+            check_auto_engine(eng)
     world = len(engines)
     shards = []
     for eng, (b, o, base) in zip(engines, parts):
@@ -864,6 +970,8 @@ def local_sharded_assemble_shards(engines, parts, k, limit=1, flags=0, partition
         partitioned = not (flags & eulerhip.EC_FLAG_GENERAL)
     if partitioned and finish == "partitioned":  # the junction-partitioned graph (junction_links)
         urs = [merge(dst, eng, False) for dst, eng in enumerate(engines)]
+        if auto_limit:
+            urs = local_auto_refilter(engines, urs, spectrum_bins, auto_info)
         sends.clear()  # (each exchange buffer is dropped once consumed: config 5's rank holds ~10^11 B)
         seg_lo = [sum(urs[:r]) for r in range(world + 1)]
         U = seg_lo[-1]
@@ -882,7 +990,12 @@ def local_sharded_assemble_shards(engines, parts, k, limit=1, flags=0, partition
         links.clear()
         segs = [(seg_lo[r], seg_lo[r + 1], None) for r in range(world)]
         return local_partitioned_finish(engines, segs, k, npal), P
-    solids = [merge(dst, eng, True) for dst, eng in enumerate(engines)]
+    if auto_limit:
+        local_auto_refilter(engines, [merge(dst, eng, False) for dst, eng in enumerate(engines)], spectrum_bins,
+                            auto_info)
+        solids = [eng.export_dense() for eng in engines]
+    else:
+        solids = [merge(dst, eng, True) for dst, eng in enumerate(engines)]
     rb = rec_bytes(k)
     mx = max(max(x.numel() for x in solids), 1)  # padded like TorchComm.allgatherv (0xFF filler records)
     allsolid = torch.full((world * mx,), 0xFF, dtype=torch.uint8, device=engines[0].device)

@@ -23,6 +23,11 @@ and the PopInfo line goes to stderr.  --auto-limit (same path) reads the solid l
 assembly's k-mer count spectrum (eulerhip.spectrum_threshold; --spectrum-bins) and re-filters the
 dict by it on the device, before the tips and bubbles; the chosen limit, or that none was found,
 goes to stderr, and --spectrum-out FILE gets the spectrum's non-zero bins as count<TAB>k-mers.
+--limit auto is the form of it that works on every path: on the fused path it is --limit 1
+--auto-limit; with --sharded or several ranks the owner merge runs at limit 1, the ranks' spectra
+of their owner segments are all-reduced, and every rank re-filters its segment by the limit read
+off the sum before the graph (distributed.sharded_assemble(auto_limit=True)); the same stderr line
+and --spectrum-out / --spectrum-bins apply.
 """
 import argparse
 import os
@@ -36,11 +41,33 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 
+def limit_arg(v):
+    """--limit: an integer, or "auto" (None)"""
+    if v == "auto":
+        return None
+    try:
+        return int(v)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r is neither an integer nor 'auto'" % v)
+
+
+def auto_limit_line(si, nbins, solid0, solid1, contigs=None):
+    """the auto-limit report of rank 0 (stderr); contigs = (before, after) where both are known"""
+    if si["found"]:
+        line = ("auto-limit: limit %d  (spectrum lo %d  descent end %d  peak %d  floor %d)  solid k-mers %d -> %d"
+                % (si["limit"], si["lo"], si["descent_end"], si["peak"], si["floor"], solid0, solid1))
+        return line + ("  contigs %d -> %d" % contigs if contigs else "")
+    return ("auto-limit: no limit found  (spectrum lo %d  descent end %d  peak %d of %d bins)  solid k-mers %d kept"
+            % (si["lo"], si["descent_end"], si["peak"], nbins, solid0))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="MI355X de Bruijn unitig assembler")
     ap.add_argument("-i", "--input", required=True, help="FASTA / FASTQ read file")
     ap.add_argument("-k", type=int, default=31, help="k-mer (node) length, 1..63")
-    ap.add_argument("--limit", type=int, default=1, help="keep k-mers seen more than this many times")
+    ap.add_argument("--limit", type=limit_arg, default=1,
+                    help="keep k-mers seen more than this many times; 'auto': count at limit 1 and choose the "
+                         "limit from the k-mer count spectrum (every path, --sharded and several ranks included)")
     ap.add_argument("-o", "--output", default="", help="contig FASTA ('>contig%%d' records)")
     ap.add_argument("--gfa", default="", help="GFA 1 output")
     ap.add_argument("--fasta-mode", choices=["records", "lines"], default="records",
@@ -63,22 +90,26 @@ def main(argv=None):
     ap.add_argument("--bubble-rounds", type=int, default=4, help="popping rounds at most (default 4)")
     ap.add_argument("--auto-limit", action="store_true",
                     help="choose the solid limit from the k-mer count spectrum of the assembly and re-filter by "
-                         "it, before --clip-tips / --pop-bubbles; one process, fused path only")
+                         "it, before --clip-tips / --pop-bubbles; one process, fused path only "
+                         "(--limit auto is the form that works on every path)")
     ap.add_argument("--spectrum-bins", type=int, default=1024,
                     help="bins of the count spectrum, 2 .. 4096 (default 1024; the last bin saturates)")
     ap.add_argument("--spectrum-out", default="",
                     help="with --auto-limit: write the spectrum's non-zero bins as count<TAB>k-mers lines")
     a = ap.parse_args(argv)
+    limit_auto = a.limit is None
+    if limit_auto:
+        a.limit = 1
     if a.auto_limit and (a.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         # (the spectrum of the sharded path would have to be all-reduced before the solid filter)
         print("euler_run: --auto-limit works on the one-process fused path only, not with --sharded or "
               "several ranks", file=sys.stderr)
         return 2
-    if a.auto_limit and not 2 <= a.spectrum_bins <= 4096:
+    if (a.auto_limit or limit_auto) and not 2 <= a.spectrum_bins <= 4096:
         print("euler_run: --spectrum-bins must be in 2 .. 4096", file=sys.stderr)
         return 2
-    if a.spectrum_out and not a.auto_limit:
-        print("euler_run: --spectrum-out needs --auto-limit", file=sys.stderr)
+    if a.spectrum_out and not (a.auto_limit or limit_auto):
+        print("euler_run: --spectrum-out needs --auto-limit or --limit auto", file=sys.stderr)
         return 2
     if a.clip_tips and (a.sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         # (the junction-partitioned graph of the sharded path holds no complete link table)
@@ -118,6 +149,8 @@ def main(argv=None):
     torch.cuda.synchronize()
     t1 = time.time()
     sharded = world > 1 or a.sharded
+    if limit_auto and not sharded:
+        a.auto_limit = True
     if not sharded:
         sess = eulerhip.Session(local, stream=torch.cuda.current_stream().cuda_stream)
         sess.run_device(d_buf.data_ptr(), d_off.data_ptr(), hi - lo, a.k, a.limit, 0)
@@ -132,14 +165,10 @@ def main(argv=None):
             if si["found"]:
                 res, _ = sess.refilter(a.k, si["limit"])
                 if rank == 0:
-                    print("auto-limit: limit %d  (spectrum lo %d  descent end %d  peak %d  floor %d)  solid k-mers "
-                          "%d -> %d  contigs %d -> %d" % (si["limit"], si["lo"], si["descent_end"], si["peak"],
-                                                          si["floor"], st0.n_solid, res.stats.n_solid, st0.n_contigs,
-                                                          res.stats.n_contigs), file=sys.stderr)
+                    print(auto_limit_line(si, a.spectrum_bins, st0.n_solid, res.stats.n_solid,
+                                          (st0.n_contigs, res.stats.n_contigs)), file=sys.stderr)
             elif rank == 0:
-                print("auto-limit: no limit found  (spectrum lo %d  descent end %d  peak %d of %d bins)  solid "
-                      "k-mers %d kept" % (si["lo"], si["descent_end"], si["peak"], a.spectrum_bins, st0.n_solid),
-                      file=sys.stderr)
+                print(auto_limit_line(si, a.spectrum_bins, st0.n_solid, st0.n_solid), file=sys.stderr)
         if a.clip_tips:
             n0 = sess.stats().n_contigs
             res, ci = sess.clip_tips(a.k, a.tip_len, a.tip_rounds)
@@ -165,7 +194,14 @@ def main(argv=None):
         else:
             dist.init_process_group("gloo")
         eng = distributed.HipEngine(local, stream=torch.cuda.current_stream().cuda_stream)
-        res, P = distributed.sharded_assemble(eng, distributed.TorchComm(), d_buf, d_off, hi - lo, lo, a.k, a.limit)
+        ai = {}
+        res, P = distributed.sharded_assemble(eng, distributed.TorchComm(), d_buf, d_off, hi - lo, lo, a.k, a.limit,
+                                              auto_limit=limit_auto, auto_info=ai, spectrum_bins=a.spectrum_bins)
+        if limit_auto and rank == 0:
+            if a.spectrum_out:
+                with open(a.spectrum_out, "w") as f:
+                    f.write("".join("%d\t%d\n" % cv for cv in sorted(ai["spectrum"].items())))
+            print(auto_limit_line(ai, a.spectrum_bins, ai["n_solid_before"], ai["n_solid_after"]), file=sys.stderr)
     torch.cuda.synchronize()
     t_asm = time.time() - t1
     if rank == 0:

@@ -178,6 +178,8 @@ _SIGS = {
     "ec_kmer_spectrum": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
     "ec_spectrum_threshold": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(SpectrumInfo)]),
     "ec_refilter": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(RefilterInfo)]),
+    "ec_dense_spectrum": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
+    "ec_dense_refilter": (ctypes.c_int, [_P, ctypes.c_uint32, ctypes.POINTER(RefilterInfo)]),
 }
 
 
