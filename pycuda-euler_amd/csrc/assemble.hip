@@ -271,12 +271,7 @@ struct ec_session {
     // without a host round trip -- k_skpart_w<., ., true> checks every read against it anyway
     const uint64_t *lc_off = nullptr;
     uint64_t lc_n = 0, lc_L = 0;
-    bool filt = false;          // phase_count: k_bucket_filt (more distinct keys than LDS tables hold)
-    int pmax = 1, pmin = 0;     // k_bucket_filt: 2^pmax part tables per bucket region
-    float part_keys = 1400.0f;  // k_bucket_filt: target keys per part table
     DevBuf bnp;                 // k_bucket_filt: per-bucket part bits
-    const unsigned long long *bbeg = nullptr, *bend = nullptr;  // launch_bucket: explicit bucket bounds
-    uint32_t nseg = 1;          // ... as nseg record ranges per bucket
     DevBuf fcur, bb2;           // count_v2.h: final-bucket cursors, bucket bounds
     DevBuf nrec;                // graph.h NodeRec: successor + first event per node (k_walk)
     SolidIndex gidx{};          // index of the loaded solid set (ec_graph_load, k <= 32)
@@ -302,11 +297,10 @@ struct ec_session {
     // copied H2D in chunks on cstream; pipe_upto(c) makes chunks .. c visible to the session
     // stream (event wait + unpack) -- the super-k-mer partition runs on each chunk's read groups
     // as they arrive, any other count path waits for all of them (pipe_all)
+    // (one copy stream: an SDMA copy runs at half its idle rate while the count kernels run
+    // (r06_i trace), and chunks alternating over two queues did not help -- pipelined 5.22 /
+    // 5.22 ms on one, 5.23 / 5.95 on two: r06_m)
     hipStream_t cstream = nullptr;
-    // a second copy stream (EULERHIP_COPY_STREAMS=2): chunks alternate between the two DMA queues.
-    // One SDMA copy runs at half its idle rate while the count kernels run (r06_i trace); two
-    // queues did not help (pipelined 5.22 / 5.22 ms on one, 5.23 / 5.95 on two: r06_m), so one
-    hipStream_t cstream2 = nullptr;
     struct Pipe {
         bool active = false;
         bool packed = false;          // 2-bit codes (k_unpack2 + k_patch) or ASCII
@@ -679,19 +673,52 @@ int compact_table(ec_session *s, SlotT *table, uint64_t cap, long long limit, Ke
 }
 
 
+// 2 U node ids (a solid k-mer and its twin) must leave bit 31 (CYC) free
+int check_node_ids(unsigned int U) {
+    if (2ull * U >= (unsigned long long)CYC) {
+        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
+        return EC_ERR_CAPACITY;
+    }
+    return EC_OK;
+}
+
+// the prescan's first byte outside {A,C,G,T,N} (Scalars::bad, ~0 = none) as EC_ERR_ALPHABET
+int check_alphabet(const uint8_t *d_reads, unsigned long long bad) {
+    if (bad == ~0ull) return EC_OK;
+    uint8_t byte = 0;
+    hipMemcpy(&byte, d_reads + bad, 1, hipMemcpyDeviceToHost);
+    set_error("byte %llu (0x%02x) outside {A,C,G,T,N}", bad, byte);
+    return EC_ERR_ALPHABET;
+}
+
+// what launch_bucket needs besides the records and the table size
+struct BucketArgs {
+    // bucket b = records [bbeg[b], bend[b]): the fixed-capacity buckets of count_v2.h; null =
+    // the exact path's scanned starts (s->bstart)
+    const unsigned long long *bbeg = nullptr, *bend = nullptr;
+    bool filt = false;             // k_bucket_filt (more distinct keys than LDS tables hold)
+    int pmin = 0, pmax = 1;        // ... with 2^pmin .. 2^pmax part tables per bucket region
+    unsigned int *bmark = nullptr; // k_bucket: one bit per dense id, set at each bucket's first
+};
+// the seen-twice filter's fields of a BucketPlan (EULERHIP_FILTER_PMIN: at least 2^pmin part tables)
+BucketArgs filter_args(bool filt, int pmax) {
+    BucketArgs a;
+    a.filt = filt;
+    a.pmax = pmax;
+    a.pmin = kn().filter_pmin >= 0 ? std::max(0, std::min(pmax, kn().filter_pmin)) : 0;
+    return a;
+}
+
 template <typename Src>
-int launch_bucket(ec_session *s, Src src, unsigned nb, unsigned slots, long long limit, unsigned int *bmark = nullptr) {
+int launch_bucket(ec_session *s, Src src, unsigned nb, unsigned slots, long long limit, BucketArgs a = {}) {
     Scalars *dsc = s->scal.as<Scalars>();
     hipStream_t st = s->stream;
-    // bucket b = records [bb[b], be[b]): the exact path's scanned starts, or the fixed-capacity
-    // buckets of count_v2.h (s->bbeg / s->bend set)
-    const unsigned long long *bb = s->bbeg ? s->bbeg : s->bstart.as<unsigned long long>();
-    const unsigned long long *be = s->bbeg ? s->bend : s->bstart.as<unsigned long long>() + 1;
-    const uint32_t ns = s->bbeg ? s->nseg : 1u;  // record ranges per bucket
-    if (s->filt) {  // error-rich input: seen-twice filter + two half tables per bucket
+    const unsigned long long *bb = a.bbeg ? a.bbeg : s->bstart.as<unsigned long long>();
+    const unsigned long long *be = a.bbeg ? a.bend : s->bstart.as<unsigned long long>() + 1;
+    if (a.filt) {  // error-rich input: seen-twice filter + two half tables per bucket
         EC_CHECK(s->bnp.ensure(nb));
         k_bucket_filt<Src><<<nb, BUCKET_THREADS, 0, st>>>(
-            src, bb, be, ns, limit, s->pmin, s->pmax, s->part_keys,
+            src, bb, be, 1u, limit, a.pmin, a.pmax, (float)PART_KEYS,
             s->dkey.as<unsigned long long>(),
             s->dcnt.as<unsigned int>(), s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(),
             s->no_index ? nullptr : s->sub.as<SubSlot>(), s->bnp.as<uint8_t>(), &dsc->nsolid, &dsc->ndistinct,
@@ -700,14 +727,14 @@ int launch_bucket(ec_session *s, Src src, unsigned nb, unsigned slots, long long
     }
     if (slots == 2048)
         k_bucket<Src, 2048><<<nb, BUCKET_THREADS, 0, st>>>(
-            src, bb, be, ns, limit, s->dkey.as<unsigned long long>(), s->dcnt.as<unsigned int>(),
+            src, bb, be, 1u, limit, s->dkey.as<unsigned long long>(), s->dcnt.as<unsigned int>(),
             s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(), s->no_index ? nullptr : s->sub.as<SubSlot>(), &dsc->nsolid,
-            &dsc->ndistinct, &dsc->overflow, bmark);
+            &dsc->ndistinct, &dsc->overflow, a.bmark);
     else
         k_bucket<Src, 4096><<<nb, BUCKET_THREADS, 0, st>>>(
-            src, bb, be, ns, limit, s->dkey.as<unsigned long long>(), s->dcnt.as<unsigned int>(),
+            src, bb, be, 1u, limit, s->dkey.as<unsigned long long>(), s->dcnt.as<unsigned int>(),
             s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(), s->no_index ? nullptr : s->sub.as<SubSlot>(), &dsc->nsolid,
-            &dsc->ndistinct, &dsc->overflow, bmark);
+            &dsc->ndistinct, &dsc->overflow, a.bmark);
     return EC_OK;
 }
 
@@ -721,12 +748,12 @@ struct BucketPlan {
     int bbits = 0;
     unsigned int slots = 2048;
 };
-BucketPlan plan_buckets(double est, long long limit, bool filt_ok) {
+BucketPlan plan_buckets(double est, long long limit) {
     constexpr int PMAX = 3;
     BucketPlan p;
     const double filt_max = limit >= 1 ? 32768.0 : PART_KEYS * (1 << PMAX);
-    p.part = est / FINE <= 2400.0 || (filt_ok && est / FINE <= filt_max);
-    p.filt = p.part && filt_ok && (est / FINE > 2400.0 || kn().force_filter);
+    p.part = est / FINE <= 2400.0 || est / FINE <= filt_max;
+    p.filt = p.part && (est / FINE > 2400.0 || kn().force_filter);
     while (p.pmax < PMAX && est / FINE / (double)(1 << p.pmax) > PART_KEYS) p.pmax++;
     if (kn().filter_pmax) p.pmax = std::max(1, std::min(PMAX, kn().filter_pmax));
     while (p.bbits < FINE_BITS && est / (double)(1ull << p.bbits) > 1100.0) p.bbits++;
@@ -777,7 +804,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
         // one a third idle; 1536 of 102 tiles run 2 full ones), at most RF_MAX_RUNS (k_skrefine)
         const uint64_t ntiles = (nreads + 63) / 64, slots = skpart_slots(npf, k - SK_M + 1, validate);
         uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>(ntiles, RF_MAX_RUNS));
-        if (g > slots && !kn().no_slot_groups) g = g / slots * slots;
+        if (g > slots) g = g / slots * slots;
         gsize = ((ntiles + g - 1) / g) * 64;
         G = (nreads + gsize - 1) / gsize;
     }
@@ -925,7 +952,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
         return reset();
     }
     const double est = hsc.est * (smask + 1.0);
-    BucketPlan plan = plan_buckets(est, limit, !kn().no_filter);
+    BucketPlan plan = plan_buckets(est, limit);
     // error-rich input (the estimate asks for the seen-twice filter): super-k-mer buckets behind
     // the filter (k_skbucket_filt) while a bucket's distinct keys stay within its 2^16 filter
     // cells (limit >= 1); otherwise window records with count_part.h's filter
@@ -1048,14 +1075,12 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
     } else if (plan.slots == 1024) {
         constexpr int NT3 = 512;
         const unsigned int claim_cap = kn().sk2_claim > 0 ? (unsigned int)kn().sk2_claim : ~0u;
-        unsigned int *bm = nullptr;
-        if (kn().tile_plan != 0) {  // (bucket starts for the tile ranking: one bit per dense id)
-            // (a whole number of 256-B lines: the runtime fills an odd tail in a second launch)
-            const size_t words = (umax / 32 + 2 + 63) & ~size_t(63);
-            EC_CHECK(s->bmark.ensure(words * 4));
-            EC_HIP(hipMemsetAsync(s->bmark.p, 0, words * 4, st));
-            bm = s->bmark.as<unsigned int>();
-        }
+        // bucket starts for the tile ranking: one bit per dense id
+        // (a whole number of 256-B lines: the runtime fills an odd tail in a second launch)
+        const size_t words = (umax / 32 + 2 + 63) & ~size_t(63);
+        EC_CHECK(s->bmark.ensure(words * 4));
+        EC_HIP(hipMemsetAsync(s->bmark.p, 0, words * 4, st));
+        unsigned int *bm = s->bmark.as<unsigned int>();
         if (dbg) {  // (EULERHIP_SK2_STATS: the instantiation with the shader-clock ticks)
             if (k & 1)
                 k_skbucket3<1024, 1664, NT3, false, true><<<(unsigned)Bk, NT3, 0, st>>>(EC_SKBUCKET_ARGS, dbg, claim_cap, bm);
@@ -1065,7 +1090,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
             k_skbucket3<1024, 1664, NT3, false><<<(unsigned)Bk, NT3, 0, st>>>(EC_SKBUCKET_ARGS, dbg, claim_cap, bm);
         else
             k_skbucket3<1024, 1664, NT3, true><<<(unsigned)Bk, NT3, 0, st>>>(EC_SKBUCKET_ARGS, dbg, claim_cap, bm);
-        b3_marked = bm != nullptr;
+        b3_marked = true;
     } else if (plan.slots == 2048) {
         if (k & 1) EC_SKBUCKET(2048, 3072, false);
         else EC_SKBUCKET(2048, 3072, true);
@@ -1193,11 +1218,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
     U = hsc.nsolid;
     s->stats.n_distinct = hsc.ndistinct;
     s->stats.n_solid = U;
-    if (2ull * U >= (unsigned long long)CYC) {
-        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
-        return EC_ERR_CAPACITY;
-    }
-    return EC_OK;
+    return check_node_ids(U);
 }
 
 // count_v2.h: the partitioned count of N-free reads of one length without the histogram
@@ -1256,12 +1277,7 @@ int phase_count_v2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off,
     mark(s, 2 * EC_STAGE_PRESCAN + 1);
     EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
     EC_CHECK(host_sync(s, st));
-    if (hsc.bad != ~0ull) {
-        uint8_t byte = 0;
-        hipMemcpy(&byte, d_reads + hsc.bad, 1, hipMemcpyDeviceToHost);
-        set_error("byte %llu (0x%02x) outside {A,C,G,T,N}", (unsigned long long)hsc.bad, byte);
-        return EC_ERR_ALPHABET;
-    }
+    EC_CHECK(check_alphabet(d_reads, hsc.bad));
     const unsigned int lmax = hsc.lens[0], lmin = ~hsc.lens[1], lall = hsc.lens[3];
     const uint64_t P = hsc.npos;
     if (hsc.lens[2] || P == 0 || lmax != lmin) return EC_OK;  // N, no windows, several lengths
@@ -1335,7 +1351,7 @@ int phase_count_v2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off,
     EC_CHECK(host_sync(s, st));
     if (hsc.overflow) return EC_OK;  // a run outgrew its capacity (extreme skew)
     const double est = hsc.est * (smask + 1.0);
-    BucketPlan plan = plan_buckets(est, limit, !kn().no_filter);
+    BucketPlan plan = plan_buckets(est, limit);
     if (!plan.part) return EC_OK;
     plan.bbits = std::max(plan.bbits, PT_CBITS);
     const int bbits = plan.bbits;
@@ -1373,36 +1389,29 @@ int phase_count_v2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off,
     EC_CHECK(s->dfc.ensure(umax * 8));
     EC_CHECK(s->dft.ensure(umax * 8));
     EC_CHECK(s->sub.ensure(umax * sizeof(SubSlot)));
-    s->pmax = plan.pmax;
-    s->part_keys = kn().part_keys > 0 ? kn().part_keys : (float)PART_KEYS;
-    s->pmin = kn().filter_pmin >= 0 ? std::max(0, std::min(plan.pmax, kn().filter_pmin)) : 0;
-    s->filt = plan.filt;
-    s->bbeg = bbeg;
-    s->bend = bend;
+    BucketArgs ba = filter_args(plan.filt, plan.pmax);
+    ba.bbeg = bbeg;
+    ba.bend = bend;
     kmark(s, 2, 0);
     const unsigned int m2 = 2 * M - 1;
-    int rc;
     auto p12 = [&](auto &src) { src.ibits = ibits, src.k = k, src.m2 = m2, src.p = s->recs2.as<unsigned int>(); };
     if (r10 && (k & 1)) {  // the refine's key words hold h = bij_fwd(key)
         Rec12PSource<false, true> src;
         p12(src);
-        rc = launch_bucket(s, src, (unsigned)Bk, plan.slots, limit);
+        EC_CHECK(launch_bucket(s, src, (unsigned)Bk, plan.slots, limit, ba));
     } else if (r10) {
         Rec12PSource<true, true> src;
         p12(src);
-        rc = launch_bucket(s, src, (unsigned)Bk, plan.slots, limit);
+        EC_CHECK(launch_bucket(s, src, (unsigned)Bk, plan.slots, limit, ba));
     } else if (k & 1) {
         Rec12PSource<false> src;
-        src.ibits = ibits, src.k = k, src.m2 = m2, src.p = s->recs2.as<unsigned int>();
-        rc = launch_bucket(s, src, (unsigned)Bk, plan.slots, limit);
+        p12(src);
+        EC_CHECK(launch_bucket(s, src, (unsigned)Bk, plan.slots, limit, ba));
     } else {
         Rec12PSource<true> src;
-        src.ibits = ibits, src.k = k, src.m2 = m2, src.p = s->recs2.as<unsigned int>();
-        rc = launch_bucket(s, src, (unsigned)Bk, plan.slots, limit);
+        p12(src);
+        EC_CHECK(launch_bucket(s, src, (unsigned)Bk, plan.slots, limit, ba));
     }
-    s->filt = false;
-    s->bbeg = s->bend = nullptr;
-    EC_CHECK(rc);
     kmark(s, 2, 1);
     mark(s, 2 * EC_STAGE_COMPACT + 1);
     EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
@@ -1433,11 +1442,7 @@ int phase_count_v2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off,
     U = hsc.nsolid;
     s->stats.n_distinct = hsc.ndistinct;
     s->stats.n_solid = U;
-    if (2ull * U >= (unsigned long long)CYC) {
-        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
-        return EC_ERR_CAPACITY;
-    }
-    return EC_OK;
+    return check_node_ids(U);
 }
 
 // build:25-42 on the device: count canonical k-mers of reads [0, nreads) (global read ids
@@ -1455,7 +1460,7 @@ int phase_count(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, ui
     Scalars *dsc = s->scal.as<Scalars>();
     Scalars hsc;
     if (!(flags & (EC_FLAG_GENERAL | EC_FLAG_WIDE_RECORDS | EC_FLAG_EXACT_COUNT)) && nreads &&
-        k <= 32 && !kn().no_v2) {
+        k <= 32) {
         bool ok = false;
         EC_CHECK(phase_count_v2(s, d_reads, d_off, nreads, read_base, k, limit, !(flags & EC_FLAG_WINDOW_RECORDS), U,
                                 sidx, ok));
@@ -1491,12 +1496,7 @@ int phase_count(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, ui
     mark(s, 2 * EC_STAGE_PRESCAN + 1);
     EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
     EC_CHECK(host_sync(s, st));
-    if (hsc.bad != ~0ull) {
-        uint8_t byte = 0;
-        hipMemcpy(&byte, d_reads + hsc.bad, 1, hipMemcpyDeviceToHost);
-        set_error("byte %llu (0x%02x) outside {A,C,G,T,N}", (unsigned long long)hsc.bad, byte);
-        return EC_ERR_ALPHABET;
-    }
+    EC_CHECK(check_alphabet(d_reads, hsc.bad));
     const uint64_t P = nreads ? hsc.npos : 0;
     s->stats.n_positions = P;
     const double est = nreads ? hsc.est : 0.0;
@@ -1508,25 +1508,14 @@ int phase_count(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, ui
     // key seen once cannot be solid by count alone (limit >= 1), up to ~32 K distinct per bucket
     // k_bucket_filt also splits a bucket into up to 2^PMAX part tables (large genomes; with
     // limit < 1 -- shard counts, no filter possible -- every key is kept)
-    constexpr int PMAX = 3;
-    const bool filt_ok = !kn().no_filter;
-    const double filt_max = limit >= 1 ? 32768.0 : PART_KEYS * (1 << PMAX);
-    bool part = !(flags & EC_FLAG_GENERAL) && nreads && P && hsc.maxlocal <= MAX_LOCAL_EVENT && !hsc.skew &&
-                (est / FINE <= 2400.0 || (filt_ok && est / FINE <= filt_max));
-    const bool filt = part && filt_ok && (est / FINE > 2400.0 || kn().force_filter);
-    int pmax = 1;  // part tables per bucket region: 2^pmax (filter mode)
-    while (pmax < PMAX && est / FINE / (double)(1 << pmax) > PART_KEYS) pmax++;
-    if (kn().filter_pmax) pmax = std::max(1, std::min(PMAX, kn().filter_pmax));
-    s->pmax = pmax;
-    s->part_keys = kn().part_keys > 0 ? kn().part_keys : (float)PART_KEYS;
-    s->pmin = kn().filter_pmin >= 0 ? std::max(0, std::min(pmax, kn().filter_pmin)) : 0;
-    int bbits = 0;
-    unsigned int slots = 2048;
+    const BucketPlan plan = plan_buckets(est, limit);
+    bool part = !(flags & EC_FLAG_GENERAL) && nreads && P && hsc.maxlocal <= MAX_LOCAL_EVENT && !hsc.skew && plan.part;
+    const bool filt = part && plan.filt;
+    const int pmax = plan.pmax, bbits = plan.bbits;
+    const unsigned int slots = plan.slots;
     sidx = SolidIndex{};
     uint64_t umax = 0;
     if (part) {
-        while (bbits < FINE_BITS && est / (double)(1ull << bbits) > 1100.0) bbits++;
-        slots = filt ? (2048u << pmax) : est / (double)(1ull << bbits) > 1100.0 ? 4096u : 2048u;
         // fewest coarse buckets the refine fan-out allows: longer downsweep runs (measured:
         // 128 vs 256 coarse buckets, k_downsweep 5.56 -> 4.98 ms at 10M x 100 bp)
         int fan = 0;
@@ -1561,8 +1550,6 @@ int phase_count(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, ui
         EC_CHECK(scan_u64(s, s->tot.as<unsigned long long>(), s->bstart.as<unsigned long long>(), Bk + 1));
         // compact records: keys [0, 8P) and meta [8P, 12P) of the first record buffer
         const Store12 c1{s->recs.as<unsigned long long>(), reinterpret_cast<unsigned int *>(s->recs.as<uint8_t>() + P * 8)};
-        // refine output of compact records: packed 12-B records
-        const bool pack12 = true;
         kmark(s, 1, 0);
         if (compact)
             k_downsweep<Rec12, MakeRec12, Store12><<<(unsigned)ngroups, TILE_READS, 0, st>>>(
@@ -1582,14 +1569,10 @@ int phase_count(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, ui
             EC_CHECK(s->gcur.ensure(Bk * 8));
             EC_HIP(hipMemcpyAsync(s->gcur.p, s->bstart.p, Bk * 8, hipMemcpyDeviceToDevice, st));
             kmark(s, 4, 0);
-            if (compact && pack12)  // 12-B in, packed 12-B out
+            if (compact)  // 12-B in, packed 12-B out
                 k_refine<Rec12, Store12, Store12P><<<dim3((unsigned)Ck, RS), BUCKET_THREADS, 0, st>>>(
                     c1, Store12P{s->recs2.as<unsigned int>()}, s->bstart.as<unsigned long long>(),
                     s->gcur.as<unsigned long long>(), cbits, bbits);
-            else if (compact)  // 12-B in, 16-B out: k_bucket reads 16-B records
-                k_refine<Rec12, Store12, Store12to16><<<dim3((unsigned)Ck, RS), BUCKET_THREADS, 0, st>>>(
-                    c1, Store12to16{s->recs2.as<Rec>(), ibits, k, (unsigned int)(2 * ((uint64_t)lmax - k + 1) - 1)},
-                    s->bstart.as<unsigned long long>(), s->gcur.as<unsigned long long>(), cbits, bbits);
             else
                 k_refine<Rec, Store16, Store16><<<dim3((unsigned)Ck, RS), BUCKET_THREADS, 0, st>>>(
                     Store16{s->recs.as<Rec>()}, Store16{s->recs2.as<Rec>()}, s->bstart.as<unsigned long long>(),
@@ -1606,34 +1589,33 @@ int phase_count(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, ui
         EC_CHECK(s->dft.ensure(umax * 8));
         EC_CHECK(s->sub.ensure(umax * sizeof(SubSlot)));
         kmark(s, 2, 0);
-        s->filt = filt;
-        if (compact && second && pack12) {
+        const BucketArgs ba = filter_args(filt, pmax);
+        if (compact && second) {
             const unsigned int m2 = (unsigned int)(2 * ((uint64_t)lmax - k + 1) - 1);
             if (k & 1) {
                 Rec12PSource<false> src;
                 src.ibits = ibits, src.k = k, src.m2 = m2, src.p = s->recs2.as<unsigned int>();
-                EC_CHECK(launch_bucket(s, src, (unsigned)Bk, slots, (long long)limit));
+                EC_CHECK(launch_bucket(s, src, (unsigned)Bk, slots, limit, ba));
             } else {
                 Rec12PSource<true> src;
                 src.ibits = ibits, src.k = k, src.m2 = m2, src.p = s->recs2.as<unsigned int>();
-                EC_CHECK(launch_bucket(s, src, (unsigned)Bk, slots, (long long)limit));
+                EC_CHECK(launch_bucket(s, src, (unsigned)Bk, slots, limit, ba));
             }
-        } else if (compact && !second) {
+        } else if (compact) {
             const unsigned int m2 = (unsigned int)(2 * ((uint64_t)lmax - k + 1) - 1);
             if (k & 1) {
                 Rec12Source<false> src;
                 src.ibits = ibits, src.k = k, src.m2 = m2, src.key = c1.key, src.meta = c1.meta;
-                EC_CHECK(launch_bucket(s, src, (unsigned)Bk, slots, (long long)limit));
+                EC_CHECK(launch_bucket(s, src, (unsigned)Bk, slots, limit, ba));
             } else {
                 Rec12Source<true> src;
                 src.ibits = ibits, src.k = k, src.m2 = m2, src.key = c1.key, src.meta = c1.meta;
-                EC_CHECK(launch_bucket(s, src, (unsigned)Bk, slots, (long long)limit));
+                EC_CHECK(launch_bucket(s, src, (unsigned)Bk, slots, limit, ba));
             }
         } else {
             EC_CHECK(launch_bucket(s, RecSource{second ? s->recs2.as<Rec>() : s->recs.as<Rec>()}, (unsigned)Bk, slots,
-                                   (long long)limit));
+                                   limit, ba));
         }
-        s->filt = false;
         kmark(s, 2, 1);
         mark(s, 2 * EC_STAGE_COMPACT + 1);
         EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
@@ -1700,11 +1682,7 @@ int phase_count(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, ui
     U = hsc.nsolid;
     s->stats.n_distinct = hsc.ndistinct;
     s->stats.n_solid = U;
-    if (2ull * U >= (unsigned long long)CYC) {
-        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
-        return EC_ERR_CAPACITY;
-    }
-    return EC_OK;
+    return check_node_ids(U);
 }
 
 // Owner-side aggregation of exchanged k-mer records (count sum, first-event min) followed by
@@ -1712,11 +1690,10 @@ int phase_count(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, ui
 // loaded for phase_graph (limit = keep all).
 // The same on the LDS bucket tables of the fused path (k_bucket over the records sorted by
 // bucket): no HBM atomics.  Returns EC_OK with ok = false when a bucket overflows its table.
-// minimizer buckets for the merge / load of 21 <= k <= 32 (shard.h OwnerFn; EULERHIP_MERGE_MIX=1:
-// key-hash buckets and owners, the round-1 layout)
-bool merge_sk(int k) { return k >= SK_MIN_K && k <= 32 && !kn().merge_mix; }
+// minimizer buckets for the merge / load of 21 <= k <= 32 (shard.h OwnerFn)
+bool merge_sk(int k) { return k >= SK_MIN_K && k <= 32; }
 // 128-bit keys on minimizer owners (the count's minimizer buckets, count_wide.h)
-bool merge_wmb(int k) { return k > 32 && k <= WMB_MAX_K && kn().wide_mb != 0 && !kn().merge_mix; }
+bool merge_wmb(int k) { return k > 32 && k <= WMB_MAX_K && kn().wide_mb != 0; }
 OwnerFn owner_fn(int k) {
     OwnerFn f{};
     f.sk = merge_sk(k) ? 1 : 0;
@@ -1793,21 +1770,21 @@ int phase_merge_part(ec_session *s, const Agg *d_agg, uint64_t n, long long limi
         EC_CHECK(launch_bucket(s, src, nb, slots, limit));
     } else {
         // (minimizer buckets: their first ids marked for the partitioned finish's tiles)
-        unsigned int *bm = nullptr;
-        if (own.sk && !s->filt && kn().tile_plan != 0) {
+        BucketArgs ba;
+        if (own.sk) {
             const size_t words = umax / 32 + 2;
             EC_CHECK(s->bmark.ensure(words * 4));
             EC_HIP(hipMemsetAsync(s->bmark.p, 0, words * 4, st));
-            bm = s->bmark.as<unsigned int>();
+            ba.bmark = s->bmark.as<unsigned int>();
         }
         if (xin) {
             const XAggSource src{*xin, s->midx2.as<unsigned int>(), sks};
-            EC_CHECK(launch_bucket(s, src, nb, slots, limit, bm));
+            EC_CHECK(launch_bucket(s, src, nb, slots, limit, ba));
         } else {
             const AggSource src{d_agg, s->midx2.as<unsigned int>(), sks};
-            EC_CHECK(launch_bucket(s, src, nb, slots, limit, bm));
+            EC_CHECK(launch_bucket(s, src, nb, slots, limit, ba));
         }
-        merge_marked = bm != nullptr;
+        merge_marked = ba.bmark != nullptr;
     }
     kmark(s, 2, 1);
     mark(s, 2 * EC_STAGE_COMPACT + 1);
@@ -1831,10 +1808,7 @@ int phase_merge_part(ec_session *s, const Agg *d_agg, uint64_t n, long long limi
     sidx.slots = slots;
     sidx.sk = own.sk;
     if (own.sk) sidx.mc = own.mc;
-    if (2ull * U >= (unsigned long long)CYC) {
-        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
-        return EC_ERR_CAPACITY;
-    }
+    EC_CHECK(check_node_ids(U));
     if (merge_marked) s->seg_marks = U;  // (bmark holds this merge's bucket starts, U ids)
     ok = true;
     return EC_OK;
@@ -1891,11 +1865,7 @@ int phase_merge(ec_session *s, const Agg *d_agg, uint64_t n, long long limit, un
     sidx = SolidIndex{};
     sidx.table = s->table.as<Slot>();
     sidx.capmask = cap - 1;
-    if (2ull * U >= (unsigned long long)CYC) {
-        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
-        return EC_ERR_CAPACITY;
-    }
-    return EC_OK;
+    return check_node_ids(U);
 }
 
 
@@ -2015,11 +1985,7 @@ int finish_wide(ec_session *s, uint64_t cap, long long limit, unsigned int &U, S
     sidx.table = s->table.as<SlotW>();
     sidx.capmask = cap - 1;
     sidx.sub = nullptr;
-    if (2ull * U >= (unsigned long long)CYC) {
-        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
-        return EC_ERR_CAPACITY;
-    }
-    return EC_OK;
+    return check_node_ids(U);
 }
 
 // Partitioned wide count (count_wide.h): upsweep, downsweep, refine and one LDS table per
@@ -2029,7 +1995,7 @@ int phase_count_wpart(ec_session *s, const uint8_t *d_reads, const uint64_t *d_o
                       uint64_t read_base, int k, long long limit, unsigned int &U, SolidIndexW &sidx, bool &ok,
                       bool mb = false, bool *mb_declined = nullptr) {
     ok = false;
-    if ((s->flags & EC_FLAG_GENERAL) || !nreads || kn().wide_general) return EC_OK;
+    if ((s->flags & EC_FLAG_GENERAL) || !nreads) return EC_OK;
     hipStream_t st = s->stream;
     const unsigned B = 256;
     Scalars *dsc = s->scal.as<Scalars>();
@@ -2069,8 +2035,8 @@ int phase_count_wpart(ec_session *s, const uint8_t *d_reads, const uint64_t *d_o
         wbv = s->wbv.as<uint32_t>();
         const unsigned g = (unsigned)((nreads + 63) / 64);
         // large inputs (the third level's run codes): k_wbv also writes the reads as 2-bit codes,
-        // from which k_run_codes copies each run's codes (EULERHIP_RUN_PACKED=0: from the ASCII)
-        if (kn().wide_runs != 0 && kn().run_packed != 0 && (uint64_t)nreads * mbM >= (1ull << 26)) {
+        // from which k_run_codes copies each run's codes
+        if (kn().wide_runs != 0 && (uint64_t)nreads * mbM >= (1ull << 26)) {
             rpack_d = (uint32_t)((L + 15) / 16);
             EC_CHECK(s->rpack.ensure((uint64_t)nreads * rpack_d * 4));
             rpack = s->rpack.as<uint32_t>();
@@ -2089,16 +2055,11 @@ int phase_count_wpart(ec_session *s, const uint8_t *d_reads, const uint64_t *d_o
     const bool runs = mb && kn().wide_runs != 0;
     // HyperLogLog sampled by minimizer past ~6.7e7 positions (as the super-k-mer count)
     const uint32_t hsmask = mb && (uint64_t)nreads * mbM >= (1ull << 26) ? 255u : 0u;
-    if (runs && kn().upsweep_staged != 1)
+    if (runs)
         k_upsweep_runs<<<(unsigned)ngroups, TILE_READS, 0, st>>>(d_reads, d_off, nreads, k, gsize,
                                                                 s->hist.as<unsigned int>(), s->hll.as<uint8_t>(),
                                                                 &dsc->npos, &dsc->maxlocal, &dsc->skew, wbv, mbM,
                                                                 hsmask);
-    else if (runs)  // (EULERHIP_UPSWEEP_STAGED=1: the staged kernel, A/B)
-        k_upsweep_w<true, true><<<(unsigned)ngroups, TILE_READS, 0, st>>>(d_reads, d_off, nreads, k, gsize,
-                                                                         s->hist.as<unsigned int>(), s->hll.as<uint8_t>(),
-                                                                         &dsc->npos, &dsc->maxlocal, &dsc->skew,
-                                                                         dsc->lens, wbv, mbM, hsmask);
     else if (mb)
         k_upsweep_w<true><<<(unsigned)ngroups, TILE_READS, 0, st>>>(d_reads, d_off, nreads, k, gsize,
                                                                    s->hist.as<unsigned int>(), s->hll.as<uint8_t>(),
@@ -2302,7 +2263,7 @@ int phase_count_wpart(ec_session *s, const uint8_t *d_reads, const uint64_t *d_o
     if (!s->no_index) EC_CHECK(s->sub.ensure(umax * sizeof(SubSlotW)));
     // minimizer buckets: each bucket's first dense id marked for the tile ranking (k_tile_plan)
     unsigned int *bm = nullptr;
-    if (mb && kn().tile_plan != 0) {
+    if (mb) {
         const size_t words = umax / 32 + 2;
         EC_CHECK(s->bmark.ensure(words * 4));
         EC_HIP(hipMemsetAsync(s->bmark.p, 0, words * 4, st));
@@ -2314,19 +2275,12 @@ int phase_count_wpart(ec_session *s, const uint8_t *d_reads, const uint64_t *d_o
         SRC, BEG, END, limit, s->dkey.as<K128>(), s->dcnt.as<unsigned int>(), s->dfc.as<unsigned long long>(),    \
         s->dft.as<unsigned long long>(), s->no_index ? nullptr : s->sub.as<SubSlotW>(), &dsc->nsolid,            \
         &dsc->ndistinct, &dsc->overflow, bm)
-#define EC_BUCKET_WR(SL, ...)                                                                                    \
-    k_bucket_wr<SL, ##__VA_ARGS__><<<(unsigned)Bt, wr_nt, 0, st>>>(                                                 \
-        rdirect, s->bb2.as<unsigned long long>(), s->bb2.as<unsigned long long>() + 1, limit, s->dkey.as<K128>(),      \
-        s->dcnt.as<unsigned int>(), s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(),                \
-        s->no_index ? nullptr : s->sub.as<SubSlotW>(), &dsc->nsolid, &dsc->ndistinct, &dsc->overflow, bm,            \
-        RunReads{d_reads, d_off, k, mbM, read_base}, wcodes, s->wcodes_tab.as<unsigned long long>())
-    // (round 6: two 79-KB workgroups a CU unless EULERHIP_WR_ONE=1 keeps round 5's one 104-KB one)
-    const bool wr_one = kn().wr_one != 0;
-    const unsigned int wr_nt = wr_one ? WR_NT : 512u;
-    if (rdirect && wr_one)
-        EC_BUCKET_WR(1664);
-    else if (rdirect)
-        EC_BUCKET_WR(1664, 512, 1024, LSlotW40);
+    if (rdirect)  // (two 79-KB workgroups a CU)
+        k_bucket_wr<1664, 512, 1024, LSlotW40><<<(unsigned)Bt, 512, 0, st>>>(
+            rdirect, s->bb2.as<unsigned long long>(), s->bb2.as<unsigned long long>() + 1, limit, s->dkey.as<K128>(),
+            s->dcnt.as<unsigned int>(), s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(),
+            s->no_index ? nullptr : s->sub.as<SubSlotW>(), &dsc->nsolid, &dsc->ndistinct, &dsc->overflow, bm,
+            RunReads{d_reads, d_off, k, mbM, read_base}, wcodes, s->wcodes_tab.as<unsigned long long>());
     else if (sbits && runs)
         EC_BUCKET_W(1664, RecWM, rwin, s->bb2.as<unsigned long long>(), s->bb2.as<unsigned long long>() + 1);
     else if (runs)
@@ -2344,7 +2298,6 @@ int phase_count_wpart(ec_session *s, const uint8_t *d_reads, const uint64_t *d_o
         EC_BUCKET_W(SLOTS_W, RecW, second ? s->recs2.as<RecW>() : s->recs.as<RecW>(), s->bstart.as<unsigned long long>(),
                     nullptr);
 #undef EC_BUCKET_W
-#undef EC_BUCKET_WR
     kmark(s, 2, 1);
     mark(s, 2 * EC_STAGE_COMPACT + 1);
     unsigned long long nruns = 0;
@@ -2372,10 +2325,7 @@ int phase_count_wpart(ec_session *s, const uint8_t *d_reads, const uint64_t *d_o
     sidx.slots = SLOTS;
     sidx.mb = mb ? 1 : 0;
     sidx.k = k;
-    if (2ull * U >= (unsigned long long)CYC) {
-        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
-        return EC_ERR_CAPACITY;
-    }
+    EC_CHECK(check_node_ids(U));
     s->bmark_ok = bm != nullptr;
     ok = true;
     return EC_OK;
@@ -2414,12 +2364,7 @@ int phase_count_w(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off, 
     mark(s, 2 * EC_STAGE_PRESCAN + 1);
     EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
     EC_CHECK(host_sync(s, st));
-    if (hsc.bad != ~0ull) {
-        uint8_t byte = 0;
-        hipMemcpy(&byte, d_reads + hsc.bad, 1, hipMemcpyDeviceToHost);
-        set_error("byte %llu (0x%02x) outside {A,C,G,T,N}", (unsigned long long)hsc.bad, byte);
-        return EC_ERR_ALPHABET;
-    }
+    EC_CHECK(check_alphabet(d_reads, hsc.bad));
     const uint64_t P = nreads ? hsc.npos : 0;
     s->stats.n_positions = P;
     const double est = nreads ? hsc.est : 0.0;
@@ -2482,13 +2427,10 @@ int order_by_minimizer_w(ec_session *s, unsigned int U) {
     EC_CHECK(s->dft.ensure((size_t)U * 8));
     EC_HIP(hipMemcpyAsync(s->dfc.p, nfc, (size_t)U * 8, hipMemcpyDeviceToDevice, st));
     EC_HIP(hipMemcpyAsync(s->dft.p, nft, (size_t)U * 8, hipMemcpyDeviceToDevice, st));
-    if (kn().tile_plan != 0) {
-        const unsigned int words = U / 32 + 2;
-        EC_CHECK(s->bmark.ensure((size_t)words * 4));
-        k_wmarks<<<grid_for(words, B), B, 0, st>>>(s->skeys2.as<unsigned long long>(), U, s->bmark.as<unsigned int>(),
-                                                   words);
-        s->seg_marks = U;
-    }
+    const unsigned int words = U / 32 + 2;
+    EC_CHECK(s->bmark.ensure((size_t)words * 4));
+    k_wmarks<<<grid_for(words, B), B, 0, st>>>(s->skeys2.as<unsigned long long>(), U, s->bmark.as<unsigned int>(), words);
+    s->seg_marks = U;
     return EC_OK;
 }
 
@@ -2793,8 +2735,7 @@ int rank_supers(ec_session *s, unsigned int M, unsigned int N, unsigned int &nr,
         EC_HIP(hipMemsetAsync(&dsc->nr, 0, 4, st));
         EC_HIP(hipMemsetAsync(&dsc->nvisited, 0, 8, st));
     }
-    unsigned int masks[4] = {15u, 3u, 1u, 0u};
-    if (kn().sruler_mask > 0) masks[0] = (unsigned int)kn().sruler_mask;  // (A/B: first-pass ruler density)
+    const unsigned int masks[4] = {15u, 3u, 1u, 0u};
     unsigned int r0 = 0;
     const unsigned int nblk = (M + RULER_CHUNK - 1) / RULER_CHUNK;
     for (int it = 0; it < 4; it++) {
@@ -2870,7 +2811,7 @@ int rank_supers_async(ec_session *s, unsigned int N, const unsigned long long *d
     const unsigned int gs = std::min(grid_for(G, B), 4096u);  // grid-stride grids over <= G items
     k_super_link<<<gs, B, 0, st>>>(srec, 0, sidx ? sidx : s->rt_sidx.as<unsigned int>(), snrec,
                                    s->rt_hasp.as<uint8_t>(), dM);
-    const unsigned int smask = kn().sruler_mask > 0 ? (unsigned int)kn().sruler_mask : 15u;
+    const unsigned int smask = 15u;
     const unsigned int nblk = (G + RULER_CHUNK - 1) / RULER_CHUNK;
     k_srulers_count<<<nblk, B, 0, st>>>(s->rt_hasp.as<uint8_t>(), 0, smask, 1, s->rid.as<uint2>(),
                                         s->rbc.as<unsigned int>(), dM);
@@ -2881,7 +2822,7 @@ int rank_supers_async(ec_session *s, unsigned int N, const unsigned long long *d
     k_walk_s<<<2048, B, 0, st>>>(snrec, s->rlist.as<unsigned int>(), 0, &dsc->nr, smask, s->rid.as<uint2>(),
                                  s->nextR.as<unsigned int>(), s->st0.as<RJump>(), &dsc->nvisited, srec);
     // rulers <= chains <= N: rounds for N (a round after convergence returns at its first load)
-    const unsigned int gr = std::min(grid_for(G / (kn().rj_div > 0 ? (unsigned)kn().rj_div : 8u) + 1, B), 2048u);
+    const unsigned int gr = std::min(grid_for(G / 8u + 1, B), 2048u);
     k_rjump_init<<<gr, B, 0, st>>>(s->nextR.as<unsigned int>(), 0, s->st0.as<RJump>(), dnr);
     rounds = 1;
     while ((1ull << (rounds - 1)) < (unsigned long long)G) rounds++;
@@ -4259,7 +4200,6 @@ int pipe_plan(ec_session *s, Pipe &pp, uint64_t nbases, uint64_t bytes_per_base4
         for (size_t i = have; i < (size_t)nc; i++) EC_HIP(hipEventCreateWithFlags(&pp.ev[i], hipEventDisableTiming));
     }
     if (!s->cstream) EC_HIP(hipStreamCreateWithFlags(&s->cstream, hipStreamNonBlocking));
-    if (!s->cstream2) EC_HIP(hipStreamCreateWithFlags(&s->cstream2, hipStreamNonBlocking));
     // the copies overwrite buffers a previous call's kernels may still read: after = the event
     // of their last reader (a staged slot), else everything queued on the session stream
     if (!after) {
@@ -4267,18 +4207,14 @@ int pipe_plan(ec_session *s, Pipe &pp, uint64_t nbases, uint64_t bytes_per_base4
         after = pp.ev[0];
     }
     EC_HIP(hipStreamWaitEvent(s->cstream, after, 0));
-    EC_HIP(hipStreamWaitEvent(s->cstream2, after, 0));
     return EC_OK;
 }
-
-// the copy stream of chunk c (EULERHIP_COPY_STREAMS=1: cstream only)
-inline hipStream_t copy_stream(ec_session *s, int c) { return (c & 1) && kn().copy_streams == 2 ? s->cstream2 : s->cstream; }
 
 // copy the offsets entries reads [r0, r1] need (chunk by chunk: [ravail[c-1] + 1, ravail[c] + 1))
 int pipe_copy_offsets(ec_session *s, const Pipe &pp, int c, const uint64_t *offsets, uint64_t *d_off) {
     const uint64_t o0 = c ? pp.ravail[c - 1] + 1 : 0, o1 = pp.ravail[c] + 1;
     if (o1 > o0)
-        EC_HIP(hipMemcpyAsync(d_off + o0, offsets + o0, (o1 - o0) * 8, hipMemcpyHostToDevice, copy_stream(s, c)));
+        EC_HIP(hipMemcpyAsync(d_off + o0, offsets + o0, (o1 - o0) * 8, hipMemcpyHostToDevice, s->cstream));
     return EC_OK;
 }
 
@@ -4363,12 +4299,11 @@ int stage_packed(ec_session *s, Pipe &pp, DevBuf &codes_b, DevBuf &exc_b, DevBuf
         // code bytes of bases [blo, bhi) (blo a multiple of 64: whole 32-bit words)
         const uint64_t c0 = pp.blo[c] / 4, c1 = c + 1 == pp.nchunks ? ncodes : pp.bhi[c] / 4;
         if (c1 > c0)
-            EC_HIP(hipMemcpyAsync(codes_b.as<uint8_t>() + c0, codes + c0, c1 - c0, hipMemcpyHostToDevice,
-                                  copy_stream(s, c)));
+            EC_HIP(hipMemcpyAsync(codes_b.as<uint8_t>() + c0, codes + c0, c1 - c0, hipMemcpyHostToDevice, s->cstream));
         if (offsets) EC_CHECK(pipe_copy_offsets(s, pp, c, offsets, off_b.as<uint64_t>()));
         pp.elo[c] = (uint64_t)(std::lower_bound(exc_pos, exc_pos + n_exc, pp.blo[c]) - exc_pos);
         pp.ehi[c] = (uint64_t)(std::lower_bound(exc_pos, exc_pos + n_exc, pp.bhi[c]) - exc_pos);
-        EC_HIP(hipEventRecord(pp.ev[c], copy_stream(s, c)));
+        EC_HIP(hipEventRecord(pp.ev[c], s->cstream));
     }
     return EC_OK;
 }
@@ -4483,7 +4418,6 @@ int ec_session_trim(ec_session *s, uint64_t min_bytes) {
     if (s->stream) EC_HIP(hipStreamSynchronize(s->stream));
     if (s->ostream) EC_HIP(hipStreamSynchronize(s->ostream));
     if (s->cstream) EC_HIP(hipStreamSynchronize(s->cstream));
-    if (s->cstream2) EC_HIP(hipStreamSynchronize(s->cstream2));
     for_each_buf(s, [&](DevBuf &b) {
         if (b.cap >= min_bytes && &b != &s->scal) b.release();
     });
@@ -4521,7 +4455,6 @@ int ec_session_destroy(ec_session *s) {
     if (s->stream) hipStreamSynchronize(s->stream);
     if (s->ostream) hipStreamSynchronize(s->ostream);
     if (s->cstream) hipStreamSynchronize(s->cstream);
-    if (s->cstream2) hipStreamSynchronize(s->cstream2);
     for_each_buf(s, [](DevBuf &b) { b.release(); });
     s->h_chars.release();
     s->hmeta.release();
@@ -4558,10 +4491,6 @@ int ec_session_destroy(ec_session *s) {
         hipStreamSynchronize(s->cstream);
         hipStreamDestroy(s->cstream);
     }
-    if (s->cstream2) {
-        hipStreamSynchronize(s->cstream2);
-        hipStreamDestroy(s->cstream2);
-    }
     if (s->own_stream && s->stream) hipStreamDestroy(s->stream);
     delete s;
     return EC_OK;
@@ -4597,9 +4526,9 @@ int ec_assemble_host(ec_session *s, const uint8_t *reads, uint64_t nbytes, const
     for (int c = 0; c < pp.nchunks; c++) {
         if (pp.bhi[c] > pp.blo[c])
             EC_HIP(hipMemcpyAsync(s->h_reads.as<uint8_t>() + pp.blo[c], reads + pp.blo[c], pp.bhi[c] - pp.blo[c],
-                                  hipMemcpyHostToDevice, copy_stream(s, c)));
+                                  hipMemcpyHostToDevice, s->cstream));
         EC_CHECK(pipe_copy_offsets(s, pp, c, offsets, s->h_offsets.as<uint64_t>()));
-        EC_HIP(hipEventRecord(pp.ev[c], copy_stream(s, c)));
+        EC_HIP(hipEventRecord(pp.ev[c], s->cstream));
     }
     return assemble_piped(s, s->h_offsets.as<uint64_t>(), nreads, k, limit, flags);
 }
@@ -5008,7 +4937,7 @@ int ec_merge_owned_from(ec_session *s, const void *d_records, int nsrc, const ui
     memcpy(s->hmeta.data() + hoff.size() * 8, hb.data(), (size_t)nsrc * 8);
     memcpy(s->hmeta.data() + hoff.size() * 8 + (size_t)nsrc * 8, hl.data(), (size_t)nsrc * 4);
     EC_HIP(hipMemcpyAsync(doff, s->hmeta.data(), mbytes, hipMemcpyHostToDevice, st));
-    if (k <= 32 && rsum && !kn().merge_decode) {
+    if (k <= 32 && rsum) {
         // k <= 32: the merge reads the received records in place; the decoded copy only for the
         // HBM-table fallback (a bucket past its LDS table, or EC_FLAG_GENERAL)
         const XIn xin{static_cast<const uint8_t *>(d_records), doff, doff + nsrc + 1, dbase, dlfb, nsrc};
@@ -5020,15 +4949,10 @@ int ec_merge_owned_from(ec_session *s, const void *d_records, int nsrc, const ui
         };
         return merge_owned_impl(s, s->xrec.p, rsum, k, limit, flags, &xin, decode);
     }
-    if (rsum) {
-        if (k > 32)
-            k_uncompact<K128><<<grid_for(rsum, 256), 256, 0, st>>>(static_cast<const uint8_t *>(d_records), doff,
-                                                                  doff + nsrc + 1, dbase, dlfb, nsrc, rsum,
-                                                                  s->xrec.as<AggW>());
-        else
-            k_uncompact<unsigned long long><<<grid_for(rsum, 256), 256, 0, st>>>(
-                static_cast<const uint8_t *>(d_records), doff, doff + nsrc + 1, dbase, dlfb, nsrc, rsum, s->xrec.as<Agg>());
-    }
+    if (rsum)  // (k > 32: the merge reads a decoded copy)
+        k_uncompact<K128><<<grid_for(rsum, 256), 256, 0, st>>>(static_cast<const uint8_t *>(d_records), doff,
+                                                              doff + nsrc + 1, dbase, dlfb, nsrc, rsum,
+                                                              s->xrec.as<AggW>());
     return ec_merge_owned(s, s->xrec.p, rsum, k, limit, flags);
 }
 
@@ -5101,10 +5025,7 @@ int ec_graph_load(ec_session *s, const void *d_records, uint64_t n, int k, unsig
         EC_CHECK(phase_load_det_w(s, reinterpret_cast<const AggW *>(d_records), n, U, s->gidxw));
     else
         EC_CHECK(phase_load_det(s, reinterpret_cast<const Agg *>(d_records), n, U, s->gidx));
-    if (2ull * U >= (unsigned long long)CYC) {
-        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
-        return EC_ERR_CAPACITY;
-    }
+    EC_CHECK(check_node_ids(U));
     s->n_dense = U;
     s->graph_loaded = true;
     s->clip_why = CLIP_WHY_STEPWISE;

@@ -23,55 +23,41 @@ void set_error(const char *fmt, ...);
 // check it (tests/conftest.py sets EULERHIP_DEBUG=1).
 struct Knobs {
     bool no_sk2 = false;        // EULERHIP_NO_SK2: no super-k-mer records (count_sk2.h)
-    bool no_v2 = false;         // EULERHIP_NO_V2: no fixed-capacity runs (count_v2.h)
     bool force_filter = false;  // EULERHIP_FORCE_FILTER: seen-twice filter buckets at any size
-    bool no_filter = false;     // EULERHIP_NO_FILTER
     int filter_pmax = 0;        // EULERHIP_FILTER_PMAX: part tables 2^pmax (0 = from the estimate)
-    int filter_pmin = -1;       // EULERHIP_FILTER_PMIN
-    float part_keys = 0.0f;     // EULERHIP_PART_KEYS: keys per part table (0 = PART_KEYS)
+    int filter_pmin = -1;       // EULERHIP_FILTER_PMIN: at least 2^pmin part tables
     int v2_r10 = -1;            // EULERHIP_V2_R10: 10-B window records 1 = forced, 0 = never
     int refine_rs = 0;          // EULERHIP_REFINE_RS: refine slices per coarse bucket (0 = 8)
     int rank_sync = 0;          // EULERHIP_RANK_SYNC=1: tile ranking with host-read counts (A/B)
-    int rj_div = 0;             // EULERHIP_RJ_DIV: rank_supers_async's Wyllie grids cover N / RJ_DIV rulers (A/B)
-    int tile_plan = -1;         // EULERHIP_TILE_PLAN=0: fixed rank tiles, not cut at bucket starts (A/B)
     int no_spec = 0;            // EULERHIP_NO_SPEC=1: no speculative launch (count_sk2's refine, the links' prologue
                                 // behind the solid count, the early character copy; A/B)
-    bool merge_mix = false;     // EULERHIP_MERGE_MIX: key-hash buckets / owners instead of minimizers
     int skf_merge = 1;          // EULERHIP_SKF_MERGE: error-rich records merged before the filter (0 off, 2 2560-entry tables)
-    bool merge_decode = false;  // EULERHIP_MERGE_DECODE: the owner merge reads a decoded copy of the received records
     int wide_runs = 1;          // EULERHIP_WIDE_RUNS: 128-bit keys on minimizer buckets partition runs (0: windows, 2: runs expanded to windows)
-    bool wide_general = false;  // EULERHIP_WIDE_GENERAL: k > 32 on the HBM table
     int wide_max_bbits = -1;    // EULERHIP_WIDE_MAX_BBITS: cap the wide buckets (forces overflow)
     int wide_l3 = 0;            // EULERHIP_WIDE_L3: third partition level of 2^n sub-buckets at any size
     long long wide_l3_cap = 0;  // EULERHIP_WIDE_L3_CAP: its sub-bucket capacity (forces its overflow)
+    int wide_mb = -1;           // EULERHIP_WIDE_MB=0: 128-bit keys bucketed by mix128, not by minimizer
     int join_links = -1;        // EULERHIP_JOIN_LINKS: links by the half-edge join 1 = always, 0 = never
+    int join_cap = 0;           // EULERHIP_JOIN_CAP: its level regions' capacity (forces the fallback)
+    int join_local = -1;        // EULERHIP_JOIN_LOCAL=0: links of minimizer-table ids by the global half-edge join
+    int join_mb = -1;           // EULERHIP_JOIN_MB=0: junctions of minimizer-bucketed keys bucketed by mix128
+    int jl_fcap = -1;           // EULERHIP_JL_FCAP: the local join's foreign-record capacity (tests: overflow)
+    int jl_bits_delta = 0;      // EULERHIP_JL_BITS_DELTA: join tables finer / coarser than the count's (tests)
     int junction_bt = -1;       // EULERHIP_JUNCTION_BT: most join bucket bits of the junction join (<= 14)
     int junction_sb = 0;        // EULERHIP_JUNCTION_SB: at least this many sub-bucket bits
     int junction_claim = 0;     // EULERHIP_JUNCTION_CLAIM: slots a join table may claim (forces overflows)
-    int no_char_pack = 0;
-    int wr_one = 0;             // EULERHIP_WR_ONE: k_bucket_wr as one 1024-thread workgroup per CU (round 5)       // EULERHIP_NO_CHAR_PACK: contig characters to host as ASCII
+    int junction_radix = -1;    // EULERHIP_JUNCTION_RADIX=1: junction buckets by the radix sort at any size
+    int no_char_pack = 0;       // EULERHIP_NO_CHAR_PACK: contig characters to host as ASCII
     int sk2_elim = 0;           // EULERHIP_SK2_ELIM: entries a k_skpart_w wave may buffer (>= 128)
-    int join_cap = 0;           // EULERHIP_JOIN_CAP: its level regions' capacity (forces the fallback)
-    int host_chunks = 0;        // EULERHIP_HOST_CHUNKS: host-input chunks (0 = ~32 MiB each)
-    bool sk2_stats = false;     // EULERHIP_SK2_STATS: k_skbucket dedup statistics on stderr
     int sk2_claim = 0;          // EULERHIP_SK2_CLAIM: k_skbucket3 record-table claim cap (tests: overflow list)
+    bool sk2_stats = false;     // EULERHIP_SK2_STATS: k_skbucket dedup statistics on stderr
     bool no_skb3 = false;       // EULERHIP_NO_SKB3: k_skbucket's 8192-bucket plan instead of k_skbucket3 (A/B)
-    bool no_slot_groups = false; // EULERHIP_NO_SLOT_GROUPS: k_skpart_w read groups not rounded to resident slots (A/B)
-    bool verbose = false;       // EULERHIP_VERBOSE: count-path fallbacks on stderr
-    int rank = -1;              // EULERHIP_RANK: list ranking 0 = tile contraction (rank_tile.h), 1 = node ruling set
     int sk_filt = -1;           // EULERHIP_SK_FILT: 0 = error-rich inputs on window records, not k_skbucket_filt
     int skf_keys = 0;           // EULERHIP_SKF_KEYS: k_skbucket_filt's keys-per-table cap (forces its overflow)
-    int wide_mb = -1;        // EULERHIP_WIDE_MB=0: 128-bit keys bucketed by mix128, not by minimizer
-    int sruler_mask = 0;     // EULERHIP_SRULER_MASK: first ruler pass of the super list takes 1 / (mask + 1)
-    int join_local = -1;
-    int junction_radix = -1;
-    int jl_fcap = -1;        // EULERHIP_JL_FCAP: the local join's foreign-record capacity (tests: overflow)
-    int jl_bits_delta = 0;   // EULERHIP_JL_BITS_DELTA: join tables finer / coarser than the count's (tests)
-    int upsweep_staged = -1;  // EULERHIP_UPSWEEP_STAGED=1: runs counted by the staged upsweep (A/B)
-    int run_packed = -1;      // EULERHIP_RUN_PACKED=0: config 5's run codes gathered from the ASCII reads
-    int copy_streams = -1;    // EULERHIP_COPY_STREAMS=2: host-input chunks alternate over two copy streams  // EULERHIP_JUNCTION_RADIX=1: junction buckets by the radix sort at any size     // EULERHIP_JOIN_LOCAL=0: links of minimizer-table ids by the global half-edge join
-    int join_mb = -1;        // EULERHIP_JOIN_MB=0: junctions of minimizer-bucketed keys bucketed by mix128
-    bool no_small_starts = false; // EULERHIP_NO_SMALL_STARTS: short lists on the general launches (k_starts_small, k_links_small off)
+    int host_chunks = 0;        // EULERHIP_HOST_CHUNKS: host-input chunks (0 = ~32 MiB each)
+    bool verbose = false;       // EULERHIP_VERBOSE: count-path fallbacks on stderr
+    int rank = -1;              // EULERHIP_RANK: list ranking 0 = tile contraction (rank_tile.h), 1 = node ruling set
+    bool no_small_starts = false;  // EULERHIP_NO_SMALL_STARTS: short lists on the general launches (k_starts_small, k_links_small off)
 };
 void refresh_knobs();
 const Knobs &kn();

@@ -95,33 +95,11 @@ struct alignas(16) SubSlot {
 };
 
 // record stores: 16-B records in one array; compact records as split arrays (8-B keys,
-// 4-B meta) so every access is an aligned, coalesced dwordx2 / dword.  Measured (10M x 100 bp):
-// k_bucket runs 1.6x longer over compact records (same instruction and LDS counts, half the
-// resident waves -- not understood), so the refine widens them back to 16 B (Store12to16):
-// compact records then save 25 % of the downsweep write and the refine read.
+// 4-B meta) so every access is an aligned, coalesced dwordx2 / dword.
 struct Store16 {
     Rec *p;
     __device__ inline Rec load(uint64_t i) const { return p[i]; }
     __device__ inline void store(uint64_t i, const Rec &r) const { p[i] = r; }
-};
-// refine output of compact records widened back to 16-B records (lC | lT events), so that
-// k_bucket reads the 16-B layout it runs fastest on
-struct Store12to16 {
-    Rec *p;
-    int ibits;
-    int k;
-    unsigned int m2;  // 2m - 1
-    __device__ inline void store(uint64_t i, const Rec12 &r) const {
-        const unsigned long long key = rkey(r);
-        const unsigned int w = r.meta & ((1u << ibits) - 1), o = (r.meta >> ibits) & 1u;
-        unsigned int lC = o ? m2 - w : w, lT = o ? w : m2 - w;
-        if (!(k & 1) && twin64(key, k) == key) lC = lT = w;  // even-k palindrome
-        Rec out;
-        out.key = key;
-        out.read = r.meta >> (ibits + 1);
-        out.ev = lC | (lT << 16);
-        p[i] = out;
-    }
 };
 
 // compact records as one packed 12-B array (the refine output read by k_bucket)

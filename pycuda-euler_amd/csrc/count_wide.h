@@ -203,9 +203,8 @@ __device__ inline void roll_w(K128 &fwd, K128 &rc, uint32_t b, const K128 &mask,
 // ---- upsweep: fine histogram (16384 bins by mix128) + HyperLogLog, per read group ----------
 // lens[2] is set when a read has an 'N' / another byte, or a tile does not fit the stage:
 // the host then counts on the HBM table instead.
-// RUNS (minimizer runs, MB only): the histogram counts run records -- a window opens one
-// where its minimizer differs from the previous window's, or the open run holds RUN_MAXW
-template <bool MB, bool RUNS = false>
+// (minimizer runs are counted by k_upsweep_runs below)
+template <bool MB>
 __global__ void __launch_bounds__(TILE_READS) k_upsweep_w(const uint8_t *buf, const uint64_t *off, uint64_t nreads,
                                                           int k, uint64_t gsize, unsigned int *hist,
                                                           uint8_t *hll_blocks, unsigned long long *npos,
@@ -216,7 +215,6 @@ __global__ void __launch_bounds__(TILE_READS) k_upsweep_w(const uint8_t *buf, co
     // (pv bits 12.., uniform) & smask are zero -- the estimate x (smask + 1), as the super-k-mer
     // count samples it; the canonical form and mix128 of the other windows are not computed
     // (config 5: the upsweep was compute-bound on them, 8 ms)
-    static_assert(MB || !RUNS, "runs need minimizer buckets");
     __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE_W + 16];
     __shared__ unsigned int h_cnt[FINE_W / 2];
     __shared__ unsigned int h_reg[1 << HLL_REG_BITS];
@@ -226,7 +224,7 @@ __global__ void __launch_bounds__(TILE_READS) k_upsweep_w(const uint8_t *buf, co
     const uint64_t g0 = group_begin(g, gsize, nreads), g1 = group_begin(g + 1, gsize, nreads);
     const K128 mask = kmask128(k);
     const int sh = 2 * (k - 1);
-    unsigned long long mypos = 0, myrec = 0;
+    unsigned long long mypos = 0;
     unsigned int mymax = 0, mynonclean = 0;
     for (uint64_t r0 = g0; r0 < g1; r0 += TILE_READS) {
         const uint64_t r1 = min(r0 + TILE_READS, g1);
@@ -254,7 +252,6 @@ __global__ void __launch_bounds__(TILE_READS) k_upsweep_w(const uint8_t *buf, co
         mymax = max(mymax, 2 * m - 1);
         K128 fwd{0, 0}, rc{0, 0};
         uint32_t c4 = 0;
-        uint32_t runv = 0, runl = 0;  // RUNS: the open run's minimizer and windows
         for (uint32_t t = 0; t < (uint32_t)len; t++) {
             if ((t & 3) == 0) c4 = rv.chunk(t >> 2);
             roll_w(fwd, rc, code2(c4 >> (8 * (t & 3))), mask, sh);
@@ -268,14 +265,7 @@ __global__ void __launch_bounds__(TILE_READS) k_upsweep_w(const uint8_t *buf, co
             }
             const uint32_t pv = MB ? pv0 : hh;
             const uint32_t f = pv >> (32 - FINE_W_BITS);
-            bool open = true;
-            if (RUNS) {
-                open = t + 1 == (uint32_t)k || pv != runv || runl == RUN_MAXW;
-                runl = open ? 1u : runl + 1;
-                runv = pv;
-                myrec += open;
-            }
-            if (open) atomicAdd(&h_cnt[f >> 1], 1u << ((f & 1) * 16));  // overflow: checked after the group
+            atomicAdd(&h_cnt[f >> 1], 1u << ((f & 1) * 16));  // overflow: checked after the group
             if (samp) {
                 const uint32_t j = hh >> (32 - HLL_REG_BITS);
                 const uint32_t rho = (uint32_t)__clz((int)((hh << HLL_REG_BITS) | (1u << (HLL_REG_BITS - 1)))) + 1;
@@ -286,7 +276,7 @@ __global__ void __launch_bounds__(TILE_READS) k_upsweep_w(const uint8_t *buf, co
     unsigned long long binsum = 0;  // bin-sum overflow check of k_upsweep
     __syncthreads();
     for (int i = threadIdx.x; i < FINE_W / 2; i += blockDim.x) binsum += (h_cnt[i] & 0xFFFFu) + (h_cnt[i] >> 16);
-    if (!RUNS) myrec = mypos;
+    unsigned long long myrec = mypos;  // a record per window
     for (int o = 32; o > 0; o >>= 1) {
         mypos += __shfl_down(mypos, o);
         myrec += __shfl_down(myrec, o);
@@ -941,8 +931,6 @@ __device__ inline void lds_insert_w(Slot *tab, unsigned int *s_over, const K128 
 // run by binary search over the window offsets, its k-mer extracted from the codes (the reverse
 // complement is ~codes, the forward string its twin) -- and inserted.  The window records never
 // exist: config 5's expansion wrote and the bucket pass read back 30 GB of them (29 + 16 ms).
-constexpr int WR_NT = 1024;        // threads a table (one workgroup per CU: 104 KB of LDS)
-constexpr int WR_CODES = 2048;     // code dwords a batch of runs stages (32 K bases)
 __device__ inline K128 extract_codes(const uint32_t *c, uint32_t bitpos) {  // bits [bitpos, bitpos + 128)
     const uint32_t w = bitpos >> 5, sft = bitpos & 31;
     uint32_t d[5];
@@ -1057,9 +1045,10 @@ __device__ inline void bucket_w_finish(const Slot *tab, unsigned int b, long lon
                                        unsigned int *nsolid, unsigned long long *ndistinct, unsigned int *bmark,
                                        unsigned int *s_wave, unsigned int *s_pres, unsigned int &s_base);
 
-// (WR_NT / WR_CODES / LSlotW: one 104-KB workgroup per CU, round 5; NT = 512, CODES = 1024,
-// LSlotW40: two 79-KB workgroups per CU, round 6)
-template <int SLOTS, int WR_NT = ::ec::WR_NT, int WR_CODES = ::ec::WR_CODES, typename Slot = LSlotW>
+// WR_NT threads a table, WR_CODES code dwords a batch of runs stages (16 bases a dword).
+// (launched with 512 threads, 1024 dwords, LSlotW40: two 79-KB workgroups per CU, round 6;
+// round 5's 1024 / 2048 / LSlotW made one 104-KB workgroup per CU and measured slower)
+template <int SLOTS, int WR_NT, int WR_CODES, typename Slot>
 __global__ void __launch_bounds__(WR_NT) k_bucket_wr(const RunWM *runs, const unsigned long long *bstart,
                                                     const unsigned long long *bend, long long limit, K128 *dkey,
                                                     unsigned int *dcnt, unsigned long long *dfc, unsigned long long *dft,
