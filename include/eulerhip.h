@@ -144,7 +144,8 @@ int ec_mem_stats(uint64_t *held, uint64_t *peak, int reset);
  * export, so the owner merge and graph phase get the count's memory (distributed.py). */
 int ec_session_trim(ec_session *s, uint64_t min_bytes);
 /* Device bytes the session's buffers hold (those ec_session_trim can release: the two staged
- * batches' device copies are not among them). */
+ * batches' device copies are not among them; the unstaged packed input's device buffers of
+ * ec_assemble_packed_host are counted and trimmed like every other). */
 uint64_t ec_session_bytes(ec_session *s);
 
 /* Reads already resident in device memory: d_reads = concatenated ASCII, d_offsets[nreads+1]

@@ -57,390 +57,7 @@
 #include <mutex>
 #include <thread>
 
-namespace ec {
-
-// ---------------------------------------------------------------------------------------
-// host side
-// device bytes the process's session buffers hold, and their high-water mark (ec_mem_stats:
-// the per-rank HBM of the sharded and streaming paths is reported from these)
-std::atomic<unsigned long long> g_hbm_held{0}, g_hbm_peak{0};
-inline void hbm_account(long long d) {
-    const unsigned long long now = g_hbm_held.fetch_add((unsigned long long)d) + (unsigned long long)d;
-    unsigned long long pk = g_hbm_peak.load();
-    while (now > pk && !g_hbm_peak.compare_exchange_weak(pk, now)) {
-    }
-}
-bool memlog_on();
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    // (spare: allocate that fraction more already the first time -- a size that varies from call
-    // to call, like the gathered chain count)
-    __attribute__((noinline)) int ensure(size_t bytes, unsigned int spare_div = 0) {
-        if (bytes <= cap) return EC_OK;
-        // a buffer that grows gets 1/8 of headroom: sizes that vary a little from call to call
-        // (chain counts, received records) would otherwise reallocate -- ~1 ms a hipFree /
-        // hipMalloc pair -- on every call that is a little larger than the last
-        size_t want = std::max<size_t>(bytes, 256);
-        if (cap) want += want / 8;
-        else if (spare_div) want += want / spare_div;
-        release();
-        const auto t0 = std::chrono::steady_clock::now();
-        if (hipMalloc(&p, want) != hipSuccess) {
-            p = nullptr;
-            set_error("hipMalloc(%zu) failed", want);
-            return EC_ERR_NOMEM;
-        }
-        cap = want;
-        hbm_account((long long)want);
-        if (want >= (1ull << 30) && memlog_on()) {  // EULERHIP_MEMLOG=1: large buffers and their call sites
-            // (lib+offset: llvm-symbolizer --obj=libeulerhip.so of the same build names the caller)
-            Dl_info di{};
-            void *ra = __builtin_return_address(0);
-            const unsigned long off = dladdr(ra, &di) && di.dli_fbase ? (unsigned long)((char *)ra - (char *)di.dli_fbase) : 0ul;
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            fprintf(stderr, "[eulerhip mem] +%.2f GB (held %.2f GB) in %.1f ms at lib+0x%lx\n", want / 1e9,
-                    g_hbm_held.load() / 1e9, ms, off);
-        }
-        return EC_OK;
-    }
-    template <typename T>
-    T *as() const { return reinterpret_cast<T *>(p); }
-    void release() {
-        if (p) {
-            const auto t0 = std::chrono::steady_clock::now();
-            hipFree(p);
-            hbm_account(-(long long)cap);
-            if (cap >= (1ull << 30) && memlog_on())
-                fprintf(stderr, "[eulerhip mem] -%.2f GB (held %.2f GB) in %.1f ms\n", cap / 1e9, g_hbm_held.load() / 1e9,
-                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        }
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-// pinned host buffer (page-locked: D2H copies of the results run at full PCIe rate)
-struct HostBuf {
-    char *p = nullptr;
-    size_t cap = 0, size = 0;
-    int resize(size_t bytes) {
-        size = bytes;
-        if (bytes <= cap) return EC_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(bytes + bytes / 4, 4096);
-        if (hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault) != hipSuccess) {
-            p = nullptr;
-            size = 0;
-            set_error("hipHostMalloc(%zu) failed", want);
-            return EC_ERR_NOMEM;
-        }
-        cap = want;
-        return EC_OK;
-    }
-    char *data() const { return p; }
-    bool empty() const { return size == 0; }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = size = 0;
-    }
-};
-
-template <typename T>
-struct PinnedVec {  // std::vector-like view of a pinned HostBuf
-    HostBuf b;
-    size_t n = 0;
-    int resize(size_t count) {
-        n = count;
-        return b.resize(count * sizeof(T));
-    }
-    T *data() const { return reinterpret_cast<T *>(b.p); }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-    T &operator[](size_t i) const { return data()[i]; }
-    void release() {
-        b.release();
-        n = 0;
-    }
-};
-
-}  // namespace ec
-
-using namespace ec;
-
-struct ec_session {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // scratch
-    DevBuf h_reads, h_offsets;  // H2D staging for ec_assemble_host
-    DevBuf hll, scal, table, dkey, dcnt, dfc, dft, upal, outdeg, cand, succ, pred, st0, st1;
-    DevBuf rid, rlist, nextR, PK, RK, PL, PM;
-    DevBuf hist, ftot, cnt, offs, bstart, tot, recs, recs2, sub;
-    DevBuf startOf, skeys, svals, skeys2, svals2, cidxOf, clen, coff, chars, cfirst, clast, headOf, tailOf;
-    DevBuf lk, lcnt, tmp, dchars, dcounts;
-    // results (host)
-    bool have = false;
-    int k = 0;
-    ec_stats stats{};
-    HostBuf h_chars;
-    // the one-GPU results' characters in transfer form: 2-bit codes, 4 a byte (A C G T = 0..3;
-    // every character of a standard-alphabet contig is one of them), nchars_host of them --
-    // ec_copy_contigs widens them (ecoli10m_err: 38 MB of characters over PCIe took ~0.7 ms)
-    bool chars_packed = false;
-    uint64_t nchars_host = 0;
-    // small device -> host reads (scalars, counts) go through this page-locked bounce buffer and
-    // are delivered by host_sync: a pageable destination cost ~11 us more per round trip
-    // (tools/micro/sync_lat.hip on MI355X: 27.2 vs 16.3 us), and a step has ~6 of them
-    HostBuf bounce;
-    struct Pend {
-        void *dst;
-        size_t off, n;
-    };
-    std::vector<Pend> pend;
-    size_t bused = 0;
-    hipEvent_t rd_ev = nullptr;  // host_wait: a read-back's event (created on first use)
-    // the contig characters' early copy to host memory (phase_graph): its stream and events, and
-    // the previous call's character total that sizes it
-    hipStream_t ostream = nullptr;
-    // oev[0] / [1]: emission done / characters copied; [2] contig offsets final; [3] link offsets final
-    hipEvent_t oev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t last_nchars = 0;
-    // bucket starts of the dense ids (k_skbucket3 marks each bucket's first id): the tile
-    // ranking cuts its tiles there (k_tile_plan); valid from a super-k-mer count to its graph phase
-    DevBuf bmark, rt_tb;
-    bool bmark_ok = false;
-    // the owner merge's marks (phase_merge_part): its solid count, 0 = none -- the partitioned
-    // finish cuts its segment's tiles there when the segment is that merge's output
-    uint64_t seg_marks = 0;
-    // count_sk2's refine plan of the previous call: launched speculatively on the next call of
-    // the same shape while the host reads the partition's scalars back (phase_count_sk2)
-    struct SkSpec {
-        bool valid = false;
-        uint64_t G = 0, cap = 0, nreads = 0, read_base = 0, fcap = 0;
-        uint32_t M = 0;
-        int k = 0, bbits = 0;
-    } skspec;
-    // links_local's first two kernels (k_jl_init, k_jl_scan) queued by phase_count_sk2 behind its
-    // bucket kernel, on the previous call's shape, while the host waits for the solid count: the
-    // scan reads U from the device and stops at ucap.  valid: links_local's shape of the previous
-    // call; queued: this call's prologue is in the stream and the count has not been redone since.
-    // Odd k only (even k needs k_upal between the two; left unspeculated)
-    struct JlSpec {
-        bool valid = false, queued = false;
-        int bits = 0, k = 0;
-        unsigned int ucap = 0, fcap = 0;
-    } jlspec;
-    DevBuf jl_frec;  // the prologue's foreign records (s->recs still feeds a second refine)
-    bool graph_follows = false;  // the call goes on to phase_graph (assemble): the prologue may run
-    // ec_spec_counts: prologues kept / run again behind the solid count's read-back [0], [1]; the
-    // same for the contig starts' read-back [2], [3], on which nothing is queued
-    uint64_t spec_cnt[4] = {0, 0, 0, 0};
-    PinnedVec<uint64_t> h_coff;  // result readbacks land in pinned host memory
-    PinnedVec<uint64_t> h_loff;
-    PinnedVec<int64_t> h_links;
-    // the one-GPU results' links in transfer form (links_compact): per-side link counts as bytes
-    // and the links as u32 (2 contig + end < 2^32) -- ec_copy_links widens them (ecoli10m_err:
-    // 18 + 18 MB of u64 offsets and links after GFA cost ~0.65 ms of PCIe; now 2.2 + 9 MB)
-    PinnedVec<uint8_t> h_lc8;
-    PinnedVec<uint32_t> h_links32;
-    bool links_compact = false;
-    // few contigs (k_links_small): link total, emission flag, contig offsets, links and link counts
-    // as one block (in dcounts on the device), copied once and taken apart on the host
-    HostBuf h_blk;
-    bool want_dict = false;
-    hipEvent_t ev[2 * EC_NSTAGES] = {};
-    hipEvent_t kev[2 * EC_NKERNELS] = {};
-    bool kused[EC_NKERNELS] = {};
-    bool sused[EC_NSTAGES] = {};
-    bool events = false;
-    bool timing = false;        // kernel events (EC_FLAG_TIMING or EC_FLAG_KERNEL_TIMING)
-    bool stage_timing = false;  // stage events (EC_FLAG_TIMING)
-    unsigned int n_dense = 0;  // dense k-mer arrays held by the session (shard / merge steps)
-    bool dense_ok = false;     // ... as ec_count_shard / ec_merge_owned left them (ec_export_* valid)
-    bool stats_ok = false;     // ec_get_stats valid (any successful call)
-    unsigned flags = 0;        // flags of the current call
-    DevBuf ocnt, rbc, mbid, mbid2, midx, midx2, gcur, cwalk, ewalk, lc8;
-    bool no_index = false;      // the call needs dense records only (shard count, owner merge)
-    uint64_t shard_base = 0;    // ec_count_shard: global id of the shard's read 0 (added at export)
-    // the super-k-mer fast path's read length of the last call on (offsets, reads): reused
-    // without a host round trip -- k_skpart_w<., ., true> checks every read against it anyway
-    const uint64_t *lc_off = nullptr;
-    uint64_t lc_n = 0, lc_L = 0;
-    DevBuf bnp;                 // k_bucket_filt: per-bucket part bits
-    DevBuf fcur, bb2;           // count_v2.h: final-bucket cursors, bucket bounds
-    DevBuf nrec;                // graph.h NodeRec: successor + first event per node (k_walk)
-    SolidIndex gidx{};          // index of the loaded solid set (ec_graph_load, k <= 32)
-    SolidIndexW gidxw{};        // the same for k > 32
-    bool graph_loaded = false;  // ec_graph_load held: ec_graph_links_part / ec_graph_finish valid
-    // junction-partitioned graph (junction.h, round 5): the segment placed at its global ids
-    // (ec_graph_place), no global set held; record / outbox scratch of the distributed join
-    bool placed = false;
-    uint64_t seg_lo = 0, seg_Ur = 0;
-    DevBuf jrec, joid, jout, jseg, jcnt;
-    DevBuf xrec;     // ec_merge_owned_from: the received records decoded
-    DevBuf skm_rec, skm_ev, skm_end;  // k_skdedup: the merged records of the error-rich count
-    DevBuf wcodes_tab;                // k_run_codes: each third-level table's first code dword
-    HostBuf hmeta;   // ... and its per-source table, staged page-locked
-    int owner_rule = 0;         // ec_session_set_owner_rule: 0 minimizer ranges (21 <= k <= 52), 1 key hash
-    // ec_export_by_owner's owner ids / scanned chunk histogram of the last call, reused by a
-    // following call with the same records, owners and rule (counts first, then the scatter)
-    bool own_valid = false;
-    int own_rule = 0, own_nowners = 0;
-    unsigned int own_n = 0, own_nblk = 0;
-    std::vector<unsigned int> own_hi;
-    // host-input pipeline (ec_assemble_host / ec_assemble_packed_host, hostin.h): the reads are
-    // copied H2D in chunks on cstream; pipe_upto(c) makes chunks .. c visible to the session
-    // stream (event wait + unpack) -- the super-k-mer partition runs on each chunk's read groups
-    // as they arrive, any other count path waits for all of them (pipe_all)
-    // (one copy stream: an SDMA copy runs at half its idle rate while the count kernels run
-    // (r06_i trace), and chunks alternating over two queues did not help -- pipelined 5.22 /
-    // 5.22 ms on one, 5.23 / 5.95 on two: r06_m)
-    hipStream_t cstream = nullptr;
-    struct Pipe {
-        bool active = false;
-        bool packed = false;          // 2-bit codes (k_unpack2 + k_patch) or ASCII
-        int nchunks = 0, done = 0;    // chunks made visible so far
-        std::vector<uint64_t> blo, bhi;   // chunk c = bases [blo[c], bhi[c]) (multiples of 64 inside)
-        std::vector<uint64_t> ravail;     // reads complete after chunk c
-        std::vector<uint64_t> elo, ehi;   // its exceptions (packed)
-        uint64_t first_len = 0;           // length of read 0 (the partition's M before any D2H)
-        const uint32_t *codes = nullptr;  // device 2-bit codes
-        const uint64_t *exc_pos = nullptr;
-        const uint8_t *exc_byte = nullptr;
-        uint8_t *ascii = nullptr;         // device reads (the count kernels' input)
-        std::vector<hipEvent_t> ev;       // chunk copy events (created on demand, reused)
-    } pipe;
-    DevBuf p_codes, p_exc;
-    // staged packed batches (ec_stage_packed_host / ec_assemble_staged): two slots, so the copy
-    // of batch i + 1 runs on cstream while batch i is assembled; free_ev = the slot's last
-    // reader (its assemble call) done on the session stream
-    struct Staged {
-        Pipe pipe;
-        DevBuf codes, exc, off;
-        hipEvent_t free_ev = nullptr;
-        uint64_t nreads = 0, nbases = 0;
-    } stg[2];
-    int stg_head = 0, stg_n = 0;
-    // extended alphabet (extended.h): its symbol table, and the one-way-link components'
-    // union-find / cut / emulation buffers
-    bool xalpha = false;
-    XAlpha xa{};
-    DevBuf x_par, x_irr, x_in, x_succ, x_done, x_lk, x_lv, x_lk2, x_lv2, x_len, x_m, x_cid, x_head, x_tail;
-    // rank_tile.h: tile counts / bases, super list, its walk records, index map, path keys / ranks
-    // join_local.h: per-key table words, table id ranges, foreign counts / offsets, flags
-    DevBuf jl_kof, jl_rs, jl_re, jl_cnt, jl_off, jl_flag;
-    DevBuf rpack;  // k_wbv's 2-bit copy of the reads (config 5's run codes gathered from it)
-    DevBuf rt_tcnt, rt_tbase, rt_srec, rt_snrec, rt_sidx, rt_pks, rt_rks, rt_hasp, rt_lr;
-    // Wyllie rounds the last converged super ranking needed + 1 (0: none yet, or it did not
-    // converge): rank_supers_async queues that many instead of ceil(log2 N) + 2 -- a round after
-    // convergence still costs its launch (~5 us; the headline needs ~18 of 26) -- and a shortfall
-    // is caught by the convergence check that already follows (the ranking redone, host-checked)
-    int spec_rounds = 0;
-    DevBuf wbv;  // count_wide.h minimizer buckets: every window's minimizer
-    // multi-GPU partitioned finish (ec_graph_chains_part ..): this rank's segment of oriented nodes
-    uint64_t seg_n0 = 0, seg_n1 = 0;
-    // a partitioned step called with a NULL output (ec_graph_place / chains_part / starts_part):
-    // its records counted and held here until the matching ec_graph_*_copy writes them into a
-    // buffer of the exact size (1: junction records, 2: super records, 3: start records)
-    struct Pending {
-        int kind = 0;
-        uint64_t n = 0;
-        unsigned int ntiles = 0;
-        bool planned = false;
-    } hold;
-    SuperRec *chain_scr = nullptr;  // part_chains' tile records (st1, or a placed segment's jrec)
-    unsigned int seg_nc = 0;     // contigs of the job (ec_graph_layout)
-    uint64_t seg_nchars = 0;
-    // the partitioned finish's transfer record (ec_graph_emit_runs / ec_graph_copy_runs):
-    // chunk counts and scans, this rank's end records, the record's sizes
-    DevBuf run_cnt, run_ends, run_dends;
-    DevBuf rt_lb;                 // k_tile_chains' look-back status words (rank_tile.h TileLB)
-    unsigned long long lb_epoch = 0;
-    uint64_t run_nr = 0, run_nch = 0, run_nends = 0;
-    bool runs_ready = false;
-    // how far the partitioned finish of the loaded / placed set has come: each step needs the one
-    // before it (0 none, 1 chains, 2 super ranking, 3 starts, 4 layout, 5 emitted)
-    int part_stage = 0;
-    // ec_clip_tips (clip.h): valid only on the results of a one-GPU graph phase whose dense arrays,
-    // lookup index, contig characters / offsets and link table are still on the device.  clip_ok is
-    // set where such a phase ends and cleared by everything that rewrites or releases them
-    // (begin_call, trim); clip_why says what the refusal reports.  cidx / cidxw: the index the
-    // count or merge returned, kept past the call (as gidx / gidxw keep a loaded set's)
-    bool clip_ok = false;
-    const char *clip_why = "a new session holds no assembly";
-    SolidIndex cidx{};
-    SolidIndexW cidxw{};
-    DevBuf clip_cand, clip_list, clip_kill, clip_tot;
-    // ec_pop_bubbles / ec_copy_contig_kmer_sums (pop.h): branch keys, per-contig sums, the tile table
-    DevBuf pop_key, pop_sum, pop_tcnt, pop_toff, pop_tile;
-    DevBuf spec_hist;  // ec_kmer_spectrum (spectrum.h): the global histogram
-};
-
-// ec_clip_tips' refusal after the stepwise calls (ec_session::clip_why)
-static const char *const CLIP_WHY_STEPWISE =
-    "the last calls were stepwise ones (ec_count_shard / ec_merge_owned* / ec_graph_*), which leave no one-GPU assembly";
-
-// Every piece of step state that points into session buffers: records held for an ec_graph_*_copy,
-// the emitted runs, the chain records' scratch, the partitioned finish's progress.  Dropped by
-// whatever releases, rewrites or may reallocate those buffers (trim, a new call, a new load /
-// place / join), so a late copy or step is refused instead of reading them (include/eulerhip.h).
-static inline void drop_step_state(ec_session *s) {
-    s->hold.kind = 0;
-    s->runs_ready = false;
-    s->chain_scr = nullptr;
-    s->part_stage = 0;
-}
-
-namespace {
-constexpr size_t BOUNCE_CAP = 64 << 10, BOUNCE_MAX = 16 << 10;  // bytes; larger reads go direct
-
-// queue a device -> host copy of n bytes to dst on st; dst is valid after host_sync(s, st)
-int d2h(ec_session *s, void *dst, const void *src, size_t n, hipStream_t st) {
-    if (!n) return EC_OK;
-    const size_t off = (s->bused + 15) & ~size_t(15);
-    if (n > BOUNCE_MAX || off + n > BOUNCE_CAP) {
-        EC_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st));
-        return EC_OK;
-    }
-    if (!s->bounce.p) EC_CHECK(s->bounce.resize(BOUNCE_CAP));
-    EC_HIP(hipMemcpyAsync(s->bounce.p + off, src, n, hipMemcpyDeviceToHost, st));
-    s->pend.push_back({dst, off, n});
-    s->bused = off + n;
-    return EC_OK;
-}
-
-// wait for event ev (recorded after the d2h copies), then deliver the queued d2h reads: the
-// stream may run on past it
-int host_wait(ec_session *s, hipEvent_t ev) {
-    const hipError_t e = hipEventSynchronize(ev);
-    for (const auto &q : s->pend) std::memcpy(q.dst, s->bounce.p + q.off, q.n);
-    s->pend.clear();
-    s->bused = 0;
-    if (e != hipSuccess) {
-        set_error("HIP error %s", hipGetErrorString(e));
-        return EC_ERR_HIP;
-    }
-    return EC_OK;
-}
-
-// wait for st, then deliver the queued d2h reads
-int host_sync(ec_session *s, hipStream_t st) {
-    const hipError_t e = hipStreamSynchronize(st);
-    for (const auto &q : s->pend) std::memcpy(q.dst, s->bounce.p + q.off, q.n);
-    s->pend.clear();
-    s->bused = 0;
-    if (e != hipSuccess) {
-        set_error("HIP error %s", hipGetErrorString(e));
-        return EC_ERR_HIP;
-    }
-    return EC_OK;
-}
-}  // namespace
+#include "session.h"
 
 namespace ec {
 
@@ -611,11 +228,9 @@ void collect_timing(ec_session *s) {
 // zeroed device scalars
 int begin_call(ec_session *s, int k, unsigned flags) {
     s->xalpha = false;  // (set by the extended-alphabet path, extended.h)
-    drop_step_state(s);
-    s->graph_loaded = false;  // (the call rewrites the buffers a loaded / placed graph lives in)
-    s->dense_ok = false;
-    s->clip_ok = false;  // (... and the dense arrays, index and results ec_clip_tips reads)
-    s->clip_why = "the session's last call failed";
+    // (the call rewrites the buffers a loaded / placed graph lives in, the dense arrays, and the
+    // index and results ec_clip_tips reads; bucket marks of an earlier call never plan its tiles)
+    drop_device_state(s, "the session's last call failed");
     refresh_knobs();
     s->have = false;
     s->stats_ok = false;
@@ -631,10 +246,6 @@ int begin_call(ec_session *s, int k, unsigned flags) {
     s->want_dict = (flags & EC_FLAG_WANT_DICT) != 0;
     s->flags = flags;
     s->shard_base = 0;
-    s->own_valid = false;
-    s->bmark_ok = false;
-    s->seg_marks = 0;  // bucket marks of an earlier call never plan this call's tiles
-    s->placed = false;
     const bool timing = (flags & (EC_FLAG_TIMING | EC_FLAG_KERNEL_TIMING)) != 0;
     s->stage_timing = (flags & EC_FLAG_TIMING) != 0;
     if (timing && !s->events) {
@@ -2940,22 +2551,21 @@ inline bool ids_minimizer_local<SolidIndexW>(const SolidIndexW &x) { return x.mb
 inline void keep_index(ec_session *s, const SolidIndex &x) { s->cidx = x; }
 inline void keep_index(ec_session *s, const SolidIndexW &x) { s->cidxw = x; }
 
-// all_contigs:79-111 on the device from the solid set of phase_count / phase_merge
+// ---- the graph phase's stages, in the order phase_graph (below) runs them ------------------------
+// links: palindrome flags and successors of the U solid k-mers' 2U oriented nodes -- the ranks'
+// partitioned links copied (ext_succ), or joined inside the count's minimizer tables
+// (join_local.h), joined globally (join_w.h), or probed (k_neighbors; after a join only where it
+// overflowed) -- then the extended alphabet's cut (nx: dict entries of its components with one-way
+// links), and for the node ranking pred with the first ruler pass's counts
 template <typename Ops, typename Index>
-int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const unsigned int *ext_succ = nullptr) {
+int graph_links(ec_session *s, int k, unsigned int U, const Index &sidx, const unsigned int *ext_succ, bool tile_rank,
+                unsigned int &nx) {
     hipStream_t st = s->stream;
     const unsigned B = 256;
     Scalars *dsc = s->scal.as<Scalars>();
-    Scalars hsc{};
     const unsigned int N = 2 * U;
     const size_t Nn = std::max<size_t>(N, 1);
-    // list ranking by tile contraction (rank_tile.h) on minimizer-local ids, the node-level
-    // ruling set otherwise (EULERHIP_RANK=1 / 2 force one or the other); tile ranking needs
-    // neither pred nor the node walk records
-    const bool tile_rank = kn().rank == 2 || (kn().rank != 1 && ids_minimizer_local(sidx));
-
-    // ---- links ----------------------------------------------------------------------------
-    mark(s, 2 * EC_STAGE_LINKS);
+    nx = 0;
     EC_CHECK(s->upal.ensure(std::max<size_t>(U, 1)));
     EC_CHECK(s->outdeg.ensure(std::max<size_t>(Nn, (Nn / 64 + 8) * 8)));  // (later: k_pred_rc's ruler bits)
     EC_CHECK(s->cand.ensure(Nn * 4));
@@ -3003,18 +2613,22 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
         k_neighbors<Ops, Index><<<gn, B, 0, st>>>(sidx, s->dkey.as<typename Ops::K>(), U, k,
                                                  s->upal.as<uint8_t>(), s->outdeg.as<uint8_t>(),
                                                  s->cand.as<unsigned int>(), joined ? nullptr : &dsc->npal, gate);
-        EC_CHECK(s->nrec.ensure(Nn * sizeof(NodeRec)));
+        // (the node records only where k_succ writes them: tile ranking never reads them, and
+        // after a join k_pred_rc writes them)
+        NodeRec *nrec = nullptr;
+        if (!(joined || tile_rank)) {
+            EC_CHECK(s->nrec.ensure(Nn * sizeof(NodeRec)));
+            nrec = s->nrec.as<NodeRec>();
+        }
         k_succ<<<gn, B, 0, st>>>(s->upal.as<uint8_t>(), s->outdeg.as<uint8_t>(), s->cand.as<unsigned int>(), N,
                                 s->succ.as<unsigned int>(), s->dfc.as<unsigned long long>(),
-                                s->dft.as<unsigned long long>(), (joined || tile_rank) ? nullptr : s->nrec.as<NodeRec>(),
-                                gate);
+                                s->dft.as<unsigned long long>(), nrec, gate);
     }
-    unsigned int nx = 0;  // extended alphabet: dict entries of components with one-way links
     if constexpr (XT) {
         if (U) EC_CHECK(x_cut(s, U, nx));
     }
     if (U && !tile_rank) {
-        // (with the first ruler pass's counts: k_rulers_count at it = 0 below is skipped, and the
+        // (with the first ruler pass's counts: rank_nodes skips k_rulers_count at it = 0, and the
         // node records when k_succ did not write them, or wrote successors x_cut has cut since)
         EC_CHECK(s->nrec.ensure(Nn * sizeof(NodeRec)));
         EC_CHECK(s->rbc.ensure(((Nn + RULER_CHUNK - 1) / RULER_CHUNK) * 8));
@@ -3023,187 +2637,187 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
             s->rbc.as<unsigned int>(), s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(),
             (ext_succ || joined || nx) ? s->nrec.as<NodeRec>() : nullptr, s->outdeg.as<unsigned long long>());
     }
-    mark(s, 2 * EC_STAGE_LINKS + 1);
+    return EC_OK;
+}
 
-    // ---- rank (sparse ruling set + weighted Wyllie on the rulers) -------------------------
-    mark(s, 2 * EC_STAGE_RANK);
-    EC_CHECK(s->rid.ensure(Nn * 8));  // (ruler, offset) per node
-    EC_CHECK(s->rlist.ensure(Nn * 4));
-    EC_CHECK(s->rbc.ensure(((Nn + RULER_CHUNK - 1) / RULER_CHUNK) * 8));
-    EC_CHECK(s->nextR.ensure(Nn * 4));
-    EC_CHECK(s->st0.ensure(Nn * sizeof(RJump)));
-    EC_CHECK(s->st1.ensure(Nn * sizeof(RJump)));
-    EC_CHECK(s->PK.ensure(Nn * 4));
-    EC_CHECK(s->RK.ensure(Nn * 4));
-    EC_CHECK(s->PL.ensure(Nn * 4));
-    EC_CHECK(s->PM.ensure(Nn * 8));
-    unsigned int nr = 0;
-    int rounds = 0;  // Wyllie rounds launched (their convergence is checked with the results)
-    bool rank_async = false;     // rank_supers_async: its checks wait for the next scalar read
-    const unsigned long long *async_M = nullptr;  // (the chain count on the device)
-    unsigned int *async_LH = nullptr, *async_LR = nullptr;
-    bool chain_paths = false;  // PK / RK of the tile ranking read through the chains (PathOf)
-    s->stats.rank_rounds = 0;
-    if (U && tile_rank) {
-        // (1) chains of in-tile links ranked in LDS, in-tile cycles finished (rank_tile.h)
-        // tiles cut at bucket starts where the count marked them (k_tile_plan), else fixed
-        const bool planned = ids_minimizer_local(sidx) && s->bmark_ok;
-        s->bmark_ok = false;
-        // (buckets of more than ~300 keys -- config 5's 2^19 tables hold ~376 -- are cut on the
-        // finer stride that may round down by up to 512: a cut inside a bucket splits nearly every
-        // minimizer run of it, whose k-mers lie in hash order across the bucket's ids)
-        const double per_bucket = s->stats.n_buckets ? (double)U / s->stats.n_buckets : 0.0;
-        const unsigned int step = per_bucket > 300.0 ? RT_STEP_SEG : RT_STEP;
-        const unsigned int ntiles = planned ? (U + step - 1) / step : (N + RT_TN - 1) / RT_TN;
-        const unsigned int *tbp = nullptr;
-        if (planned) {
-            EC_CHECK(s->rt_tb.ensure(((size_t)ntiles + 1) * 4));
-            k_tile_plan<<<grid_for(ntiles + 1ull, B), B, 0, st>>>(s->bmark.as<unsigned int>(), U, ntiles,
-                                                               s->rt_tb.as<unsigned int>(), 0u, step);
-            tbp = s->rt_tb.as<unsigned int>();
-        }
-        EC_CHECK(s->rt_tcnt.ensure(((size_t)ntiles + 1) * 8));
-        EC_CHECK(s->rt_tbase.ensure(((size_t)ntiles + 1) * 8));
-        EC_CHECK(s->rt_srec.ensure(Nn * sizeof(SuperRec)));
-        EC_CHECK(s->rt_sidx.ensure(Nn * 4));
-        EC_CHECK(s->rt_lr.ensure(Nn * 4));
-        unsigned int *LH = s->pred.as<unsigned int>(), *LR = s->rt_lr.as<unsigned int>();  // (pred: free here)
-        // (a planned tile keeps its chain records at its first node's offset, tb[t] - tb[0]: its
-        // chains fit in its nodes, so N records suffice; fixed tiles at scratch[tile * RT_TN ..])
-        EC_CHECK(s->st1.ensure(std::max<size_t>(Nn, planned ? 0 : (size_t)ntiles * RT_TN) * sizeof(RJump)));
-        SuperRec *scratch = reinterpret_cast<SuperRec *>(s->st1.p);  // (dead before the Wyllie rounds)
-        static_assert(sizeof(SuperRec) == sizeof(RJump), "tile scratch in the ruler state buffer");
-        unsigned long long *tcnt = s->rt_tcnt.as<unsigned long long>(), *tbase = s->rt_tbase.as<unsigned long long>();
-        EC_CHECK(s->rt_hasp.ensure(Nn));  // (sized here: k_tile_compact initialises it for rank_supers)
-        // (2) the super list: compacted in tile order, linked, ranked by the weighted ruling set
-        // (round 4 measured the same sequence as one cooperative launch: rank stage 0.63 -> 3.3
-        // ms, its grid barriers far slower than the launches they replace; removed in round 5)
-        unsigned int M = 0;
-        rank_async = kn().rank_sync != 1;
-        async_LH = LH;
-        async_LR = LR;
-        if (rank_async) {  // no read-back: the checks ride on the scalar read after the starts
-            // the chains compacted by look-back in k_tile_chains itself (round 6: no scan, no
-            // k_tile_compact, LH = super index); the status words are cleared once per allocation
-            // (a reallocation is told by the capacity: the new block may come back at the old address)
-            const size_t oldcap = s->rt_lb.cap;
-            EC_CHECK(s->rt_lb.ensure(((size_t)ntiles + 1) * 8));
-            if (s->rt_lb.cap != oldcap) {
-                EC_HIP(hipMemsetAsync(s->rt_lb.p, 0, s->rt_lb.cap, st));
-                s->lb_epoch = 0;
-            }
-            s->lb_epoch = (s->lb_epoch + 1) & ((1ull << 30) - 1);
-            if (s->lb_epoch == 0) {  // (wrapped: words of 2^30 calls ago could match)
-                EC_HIP(hipMemsetAsync(s->rt_lb.p, 0, s->rt_lb.cap, st));
-                s->lb_epoch = 1;
-            }
-            TileLB lb{s->rt_lb.as<unsigned long long>(), s->lb_epoch, s->rt_srec.as<SuperRec>(),
-                      s->rt_hasp.as<uint8_t>(), s->rid.as<uint2>(), &dsc->chains, &dsc->nr, &dsc->nvisited};
-            async_M = &dsc->chains;
-            k_tile_chains<<<ntiles, RT_NT, 0, st>>>(s->upal.as<uint8_t>(), s->succ.as<unsigned int>(), N,
-                                                    s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(),
-                                                    LH, LR, tcnt, scratch, s->PK.as<unsigned int>(),
-                                                    s->RK.as<unsigned int>(), s->PL.as<unsigned int>(),
-                                                    s->PM.as<unsigned long long>(), 0u, tbp, lb);
-            EC_CHECK(rank_supers_async(s, N, async_M, rounds, 0, LH));
-            // (3) no k_expand: every reader takes a node's key and rank from its chain (PathOf)
-            chain_paths = true;
-        } else {
-            k_tile_chains<<<ntiles, RT_NT, 0, st>>>(s->upal.as<uint8_t>(), s->succ.as<unsigned int>(), N,
-                                                    s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(),
-                                                    LH, LR, tcnt, scratch, s->PK.as<unsigned int>(),
-                                                    s->RK.as<unsigned int>(), s->PL.as<unsigned int>(),
-                                                    s->PM.as<unsigned long long>(), 0u, tbp);
-            EC_CHECK(scan_u64(s, tcnt, tbase, (size_t)ntiles + 1));
-            // the chain count read back while k_tile_compact (sized by the tiles, not by M) runs:
-            // the host's wake-up and next launches overlap the compaction
-            unsigned long long M64 = 0;
-            if (!s->rd_ev) EC_HIP(hipEventCreateWithFlags(&s->rd_ev, hipEventDisableTiming));
-            EC_CHECK(d2h(s, &M64, tbase + ntiles, 8, st));
-            EC_HIP(hipEventRecord(s->rd_ev, st));
-            k_tile_compact<<<ntiles, 256, 0, st>>>(scratch, tcnt, tbase, s->rt_srec.as<SuperRec>(),
-                                                   s->rt_sidx.as<unsigned int>(), s->rt_hasp.as<uint8_t>(),
-                                                   s->rid.as<uint2>(), &dsc->nr, &dsc->nvisited, nullptr, tbp);
-            EC_CHECK(host_wait(s, s->rd_ev));
-            M = (unsigned int)M64;
-        }
-        if (!rank_async && M) {
-            EC_CHECK(rank_supers(s, M, N, nr, rounds, true));
-            // (3) every node: its chain's key and rank + its offset in the chain
-            k_expand<<<grid_for(N, B), B, 0, st>>>(LH, LR, N, s->rt_sidx.as<unsigned int>(), s->rt_pks.as<unsigned int>(),
-                                                  s->rt_rks.as<unsigned int>(), s->PK.as<unsigned int>(),
-                                                  s->RK.as<unsigned int>());
-        }
+// what a ranking leaves for the starts
+struct Ranked {
+    unsigned int nr = 0;  // rulers
+    int rounds = 0;       // Wyllie rounds launched (their convergence is checked with the results)
+    // rank_tiles only.  async: rank_supers_async ran, and its checks (every chain visited, the
+    // rounds converged) wait for the starts' scalar read; chain_paths: PK / RK are read through
+    // the chains (PathOf over LH / LR) instead of expanded per node
+    bool async = false, chain_paths = false;
+    unsigned int *LH = nullptr, *LR = nullptr;
+};
+
+// rank by tile contraction (rank_tile.h), on minimizer-local ids
+template <typename Index>
+int rank_tiles(ec_session *s, unsigned int U, const Index &sidx, Ranked &r) {
+    hipStream_t st = s->stream;
+    const unsigned B = 256;
+    Scalars *dsc = s->scal.as<Scalars>();
+    const unsigned int N = 2 * U;
+    const size_t Nn = std::max<size_t>(N, 1);
+    // (1) chains of in-tile links ranked in LDS, in-tile cycles finished (rank_tile.h)
+    // tiles cut at bucket starts where the count marked them (k_tile_plan), else fixed
+    const bool planned = ids_minimizer_local(sidx) && s->bmark_ok;
+    s->bmark_ok = false;
+    // (buckets of more than ~300 keys -- config 5's 2^19 tables hold ~376 -- are cut on the
+    // finer stride that may round down by up to 512: a cut inside a bucket splits nearly every
+    // minimizer run of it, whose k-mers lie in hash order across the bucket's ids)
+    const double per_bucket = s->stats.n_buckets ? (double)U / s->stats.n_buckets : 0.0;
+    const unsigned int step = per_bucket > 300.0 ? RT_STEP_SEG : RT_STEP;
+    const unsigned int ntiles = planned ? (U + step - 1) / step : (N + RT_TN - 1) / RT_TN;
+    const unsigned int *tbp = nullptr;
+    if (planned) {
+        EC_CHECK(s->rt_tb.ensure(((size_t)ntiles + 1) * 4));
+        k_tile_plan<<<grid_for(ntiles + 1ull, B), B, 0, st>>>(s->bmark.as<unsigned int>(), U, ntiles,
+                                                           s->rt_tb.as<unsigned int>(), 0u, step);
+        tbp = s->rt_tb.as<unsigned int>();
     }
-    if (U && !tile_rank) {
-        EC_HIP(hipMemsetAsync(s->rid.p, 0xFF, Nn * 8, st));
-        EC_CHECK(s->nrec.ensure(Nn * sizeof(NodeRec)));
-        unsigned int masks[4] = {31u, 7u, 1u, 0u};
-        unsigned int r0 = 0;
-        for (int it = 0; it < 4; it++) {
-            const unsigned int nblk = (unsigned int)((N + RULER_CHUNK - 1) / RULER_CHUNK);
-            if (it)  // (it = 0: counted by k_pred_rc with masks[0])
-                k_rulers_count<<<nblk, B, 0, st>>>(s->upal.as<uint8_t>(), s->pred.as<unsigned int>(), N, masks[it],
-                                                   it == 0, s->rid.as<uint2>(), s->rbc.as<unsigned int>());
-            EC_CHECK(scan_incl_u32(s, s->rbc.as<unsigned int>(), s->rbc.as<unsigned int>() + nblk, nblk));
-            k_rulers<<<nblk, B, 0, st>>>(s->upal.as<uint8_t>(), s->pred.as<unsigned int>(), N, masks[it], it == 0,
-                                         s->rbc.as<unsigned int>() + nblk, &dsc->nr, s->rid.as<uint2>(),
-                                         s->rlist.as<unsigned int>(),
-                                         it == 0 ? s->outdeg.as<unsigned long long>() : nullptr);
-            k_rulers_total<<<1, 1, 0, st>>>(s->rbc.as<unsigned int>() + nblk, nblk, &dsc->nr);
-            k_walk<<<2048, B, 0, st>>>(s->nrec.as<NodeRec>(), s->rlist.as<unsigned int>(), r0, &dsc->nr,
-                                      masks[it], s->rid.as<uint2>(),
-                                      s->nextR.as<unsigned int>(), s->st0.as<RJump>(), &dsc->nvisited);
-            EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
-            EC_CHECK(host_sync(s, st));
-            r0 = hsc.nr;
-            if (hsc.nvisited + hsc.npal >= N) break;
+    EC_CHECK(s->rt_tcnt.ensure(((size_t)ntiles + 1) * 8));
+    EC_CHECK(s->rt_tbase.ensure(((size_t)ntiles + 1) * 8));
+    EC_CHECK(s->rt_srec.ensure(Nn * sizeof(SuperRec)));
+    EC_CHECK(s->rt_sidx.ensure(Nn * 4));
+    EC_CHECK(s->rt_lr.ensure(Nn * 4));
+    unsigned int *LH = s->pred.as<unsigned int>(), *LR = s->rt_lr.as<unsigned int>();  // (pred: free here)
+    // (a planned tile keeps its chain records at its first node's offset, tb[t] - tb[0]: its
+    // chains fit in its nodes, so N records suffice; fixed tiles at scratch[tile * RT_TN ..])
+    EC_CHECK(s->st1.ensure(std::max<size_t>(Nn, planned ? 0 : (size_t)ntiles * RT_TN) * sizeof(RJump)));
+    SuperRec *scratch = reinterpret_cast<SuperRec *>(s->st1.p);  // (dead before the Wyllie rounds)
+    static_assert(sizeof(SuperRec) == sizeof(RJump), "tile scratch in the ruler state buffer");
+    unsigned long long *tcnt = s->rt_tcnt.as<unsigned long long>(), *tbase = s->rt_tbase.as<unsigned long long>();
+    EC_CHECK(s->rt_hasp.ensure(Nn));  // (sized here: k_tile_compact initialises it for rank_supers)
+    // (2) the super list: compacted in tile order, linked, ranked by the weighted ruling set
+    // (round 4 measured the same sequence as one cooperative launch: rank stage 0.63 -> 3.3
+    // ms, its grid barriers far slower than the launches they replace; removed in round 5)
+    unsigned int M = 0;
+    r.async = kn().rank_sync != 1;
+    r.LH = LH;
+    r.LR = LR;
+    if (r.async) {  // no read-back: the checks ride on the scalar read after the starts
+        // the chains compacted by look-back in k_tile_chains itself (round 6: no scan, no
+        // k_tile_compact, LH = super index); the status words are cleared once per allocation
+        // (a reallocation is told by the capacity: the new block may come back at the old address)
+        const size_t oldcap = s->rt_lb.cap;
+        EC_CHECK(s->rt_lb.ensure(((size_t)ntiles + 1) * 8));
+        if (s->rt_lb.cap != oldcap) {
+            EC_HIP(hipMemsetAsync(s->rt_lb.p, 0, s->rt_lb.cap, st));
+            s->lb_epoch = 0;
         }
-        nr = hsc.nr;
-        if (hsc.nvisited + hsc.npal != N) {
-            set_error("ruling set covered %llu of %u nodes", (unsigned long long)(hsc.nvisited + hsc.npal), N);
-                return EC_ERR_STATE;
+        s->lb_epoch = (s->lb_epoch + 1) & ((1ull << 30) - 1);
+        if (s->lb_epoch == 0) {  // (wrapped: words of 2^30 calls ago could match)
+            EC_HIP(hipMemsetAsync(s->rt_lb.p, 0, s->rt_lb.cap, st));
+            s->lb_epoch = 1;
         }
-        k_rjump_init<<<grid_for(nr, B), B, 0, st>>>(s->nextR.as<unsigned int>(), nr, s->st0.as<RJump>());
-        rounds = 1;
-        while ((1ull << (rounds - 1)) < (unsigned long long)nr) rounds++;
-        rounds = std::min(rounds + 1, 63);
-        RJump *bufs[2] = {s->st0.as<RJump>(), s->st1.as<RJump>()};
-        for (int r = 0; r < rounds; r++)
-            k_rjump<<<grid_for(nr, B), B, 0, st>>>(bufs[r & 1], bufs[(r + 1) & 1], nr, N,
-                                                  r ? &dsc->active[r - 1] : nullptr, &dsc->active[r],
-                                                  &dsc->final_sel, (unsigned)((r + 1) & 1));
-        k_finalize<<<grid_for(N, B), B, 0, st>>>(s->upal.as<uint8_t>(), s->succ.as<unsigned int>(),
-                                                s->rid.as<uint2>(), s->rlist.as<unsigned int>(), bufs[0], bufs[1],
-                                                &dsc->final_sel, &dsc->active[rounds - 1], N, s->PK.as<unsigned int>(),
+        TileLB lb{s->rt_lb.as<unsigned long long>(), s->lb_epoch, s->rt_srec.as<SuperRec>(),
+                  s->rt_hasp.as<uint8_t>(), s->rid.as<uint2>(), &dsc->chains, &dsc->nr, &dsc->nvisited};
+        k_tile_chains<<<ntiles, RT_NT, 0, st>>>(s->upal.as<uint8_t>(), s->succ.as<unsigned int>(), N,
+                                                s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(),
+                                                LH, LR, tcnt, scratch, s->PK.as<unsigned int>(),
                                                 s->RK.as<unsigned int>(), s->PL.as<unsigned int>(),
-                                                s->PM.as<unsigned long long>());
-        k_cycle_len<<<grid_for(nr, B), B, 0, st>>>(s->nextR.as<unsigned int>(), s->rlist.as<unsigned int>(), bufs[0],
-                                                  bufs[1], &dsc->final_sel, &dsc->active[rounds - 1], nr,
-                                                  s->PL.as<unsigned int>(),
-                                                  s->PM.as<unsigned long long>());
+                                                s->PM.as<unsigned long long>(), 0u, tbp, lb);
+        EC_CHECK(rank_supers_async(s, N, &dsc->chains, r.rounds, 0, LH));
+        // (3) no k_expand: every reader takes a node's key and rank from its chain (PathOf)
+        r.chain_paths = true;
+    } else {
+        k_tile_chains<<<ntiles, RT_NT, 0, st>>>(s->upal.as<uint8_t>(), s->succ.as<unsigned int>(), N,
+                                                s->dfc.as<unsigned long long>(), s->dft.as<unsigned long long>(),
+                                                LH, LR, tcnt, scratch, s->PK.as<unsigned int>(),
+                                                s->RK.as<unsigned int>(), s->PL.as<unsigned int>(),
+                                                s->PM.as<unsigned long long>(), 0u, tbp);
+        EC_CHECK(scan_u64(s, tcnt, tbase, (size_t)ntiles + 1));
+        // the chain count read back while k_tile_compact (sized by the tiles, not by M) runs:
+        // the host's wake-up and next launches overlap the compaction
+        unsigned long long M64 = 0;
+        if (!s->rd_ev) EC_HIP(hipEventCreateWithFlags(&s->rd_ev, hipEventDisableTiming));
+        EC_CHECK(d2h(s, &M64, tbase + ntiles, 8, st));
+        EC_HIP(hipEventRecord(s->rd_ev, st));
+        k_tile_compact<<<ntiles, 256, 0, st>>>(scratch, tcnt, tbase, s->rt_srec.as<SuperRec>(),
+                                               s->rt_sidx.as<unsigned int>(), s->rt_hasp.as<uint8_t>(),
+                                               s->rid.as<uint2>(), &dsc->nr, &dsc->nvisited, nullptr, tbp);
+        EC_CHECK(host_wait(s, s->rd_ev));
+        M = (unsigned int)M64;
     }
-    s->stats.n_rulers = nr;
-    mark(s, 2 * EC_STAGE_RANK + 1);
+    if (!r.async && M) {
+        EC_CHECK(rank_supers(s, M, N, r.nr, r.rounds, true));
+        // (3) every node: its chain's key and rank + its offset in the chain
+        k_expand<<<grid_for(N, B), B, 0, st>>>(LH, LR, N, s->rt_sidx.as<unsigned int>(), s->rt_pks.as<unsigned int>(),
+                                              s->rt_rks.as<unsigned int>(), s->PK.as<unsigned int>(),
+                                              s->RK.as<unsigned int>());
+    }
+    return EC_OK;
+}
 
-    // ---- starts + order -------------------------------------------------------------------
-    const PathOf P = chain_paths ? PathOf{s->PK.as<unsigned int>(), s->RK.as<unsigned int>(), async_LH, async_LR,
-                                          s->rt_pks.as<unsigned int>(), s->rt_rks.as<unsigned int>()}
-                                 : path_of(s->PK.as<unsigned int>(), s->RK.as<unsigned int>());
-    mark(s, 2 * EC_STAGE_STARTS);
-    EC_CHECK(s->cidxOf.ensure(Nn * 4));
-    EC_CHECK(s->skeys.ensure(Nn * 8));
-    EC_CHECK(s->svals.ensure(Nn * 4));
-    EC_CHECK(s->skeys2.ensure(Nn * 8));
-    EC_CHECK(s->svals2.ensure(Nn * 4));
-    // the emission's node maps are cleared behind the starts' read-back copy (below): the device
-    // works through the fills while the host wakes up; the start kernels read none of them
-    EC_CHECK(s->headOf.ensure(Nn * 4));
-    EC_CHECK(s->tailOf.ensure(Nn * 4));
-    unsigned long long async_M64 = 0;
-    auto starts_pass = [&]() -> int {
-    if (U)
-    {
+// rank by the node-level ruling set: up to four host-checked ruler passes, weighted Wyllie on the
+// rulers
+int rank_nodes(ec_session *s, unsigned int U, unsigned int &nr, int &rounds) {
+    hipStream_t st = s->stream;
+    const unsigned B = 256;
+    Scalars *dsc = s->scal.as<Scalars>();
+    const unsigned int N = 2 * U;
+    const size_t Nn = std::max<size_t>(N, 1);
+    Scalars hsc{};
+    EC_HIP(hipMemsetAsync(s->rid.p, 0xFF, Nn * 8, st));
+    EC_CHECK(s->nrec.ensure(Nn * sizeof(NodeRec)));
+    unsigned int masks[4] = {31u, 7u, 1u, 0u};
+    unsigned int r0 = 0;
+    for (int it = 0; it < 4; it++) {
+        const unsigned int nblk = (unsigned int)((N + RULER_CHUNK - 1) / RULER_CHUNK);
+        if (it)  // (it = 0: counted by k_pred_rc with masks[0])
+            k_rulers_count<<<nblk, B, 0, st>>>(s->upal.as<uint8_t>(), s->pred.as<unsigned int>(), N, masks[it],
+                                               it == 0, s->rid.as<uint2>(), s->rbc.as<unsigned int>());
+        EC_CHECK(scan_incl_u32(s, s->rbc.as<unsigned int>(), s->rbc.as<unsigned int>() + nblk, nblk));
+        k_rulers<<<nblk, B, 0, st>>>(s->upal.as<uint8_t>(), s->pred.as<unsigned int>(), N, masks[it], it == 0,
+                                     s->rbc.as<unsigned int>() + nblk, &dsc->nr, s->rid.as<uint2>(),
+                                     s->rlist.as<unsigned int>(),
+                                     it == 0 ? s->outdeg.as<unsigned long long>() : nullptr);
+        k_rulers_total<<<1, 1, 0, st>>>(s->rbc.as<unsigned int>() + nblk, nblk, &dsc->nr);
+        k_walk<<<2048, B, 0, st>>>(s->nrec.as<NodeRec>(), s->rlist.as<unsigned int>(), r0, &dsc->nr,
+                                  masks[it], s->rid.as<uint2>(),
+                                  s->nextR.as<unsigned int>(), s->st0.as<RJump>(), &dsc->nvisited);
+        EC_CHECK(d2h(s, &hsc, dsc, sizeof(Scalars), st));
+        EC_CHECK(host_sync(s, st));
+        r0 = hsc.nr;
+        if (hsc.nvisited + hsc.npal >= N) break;
+    }
+    nr = hsc.nr;
+    if (hsc.nvisited + hsc.npal != N) {
+        set_error("ruling set covered %llu of %u nodes", (unsigned long long)(hsc.nvisited + hsc.npal), N);
+        return EC_ERR_STATE;
+    }
+    k_rjump_init<<<grid_for(nr, B), B, 0, st>>>(s->nextR.as<unsigned int>(), nr, s->st0.as<RJump>());
+    rounds = 1;
+    while ((1ull << (rounds - 1)) < (unsigned long long)nr) rounds++;
+    rounds = std::min(rounds + 1, 63);
+    RJump *bufs[2] = {s->st0.as<RJump>(), s->st1.as<RJump>()};
+    for (int r = 0; r < rounds; r++)
+        k_rjump<<<grid_for(nr, B), B, 0, st>>>(bufs[r & 1], bufs[(r + 1) & 1], nr, N,
+                                              r ? &dsc->active[r - 1] : nullptr, &dsc->active[r],
+                                              &dsc->final_sel, (unsigned)((r + 1) & 1));
+    k_finalize<<<grid_for(N, B), B, 0, st>>>(s->upal.as<uint8_t>(), s->succ.as<unsigned int>(),
+                                            s->rid.as<uint2>(), s->rlist.as<unsigned int>(), bufs[0], bufs[1],
+                                            &dsc->final_sel, &dsc->active[rounds - 1], N, s->PK.as<unsigned int>(),
+                                            s->RK.as<unsigned int>(), s->PL.as<unsigned int>(),
+                                            s->PM.as<unsigned long long>());
+    k_cycle_len<<<grid_for(nr, B), B, 0, st>>>(s->nextR.as<unsigned int>(), s->rlist.as<unsigned int>(), bufs[0],
+                                              bufs[1], &dsc->final_sel, &dsc->active[rounds - 1], nr,
+                                              s->PL.as<unsigned int>(),
+                                              s->PM.as<unsigned long long>());
+    return EC_OK;
+}
+
+// the contig starts (nodes with their component's smallest first event) as sort pairs, and the
+// scalars read back (hsc: nstarts, active[], the chain count) while the emission's node maps are
+// cleared; run again after the ranking had to be redone
+int starts_pass(ec_session *s, unsigned int U, const PathOf &P, unsigned int nx, Scalars &hsc) {
+    hipStream_t st = s->stream;
+    const unsigned B = 256;
+    Scalars *dsc = s->scal.as<Scalars>();
+    const unsigned int N = 2 * U;
+    const size_t Nn = std::max<size_t>(N, 1);
+    if (U) {
         const unsigned int nblk = (unsigned int)((N + RULER_CHUNK - 1) / RULER_CHUNK);
         unsigned int *bc = s->rbc.as<unsigned int>(), *bs = bc + nblk;
         // the start bits between the two passes live in `cand` (free after the links)
@@ -3227,198 +2841,29 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
     k_emit_init<<<grid_for(Nn / 4 + 1, B, 2048), B, 0, st>>>(s->headOf.as<unsigned int>(), s->tailOf.as<unsigned int>(),
                                                             s->cidxOf.as<unsigned int>(), Nn, &dsc->skew);
     EC_CHECK(host_wait(s, s->rd_ev));
-    async_M64 = hsc.chains;
     return EC_OK;
-    };
-    EC_CHECK(starts_pass());
-    if (rank_async) {
-        const unsigned int Ma = (unsigned int)async_M64;
-        nr = hsc.nr;
-        s->stats.n_rulers = nr;
-        if (kn().verbose)
-            fprintf(stderr, "rank: %u oriented nodes, %u chains (tile contraction), %u rulers, %llu visited\n", N, Ma,
-                    nr, (unsigned long long)hsc.nvisited);
-        if (Ma) note_rounds(s, hsc, rounds);
-        if (hsc.nvisited != Ma || (Ma && hsc.active[rounds - 1] != 0)) {
-            // a cycle of chains no ruler reached (or unconverged rounds): the ranking with its
-            // host-checked ruler passes, then the starts again
-            if (kn().verbose)
-                fprintf(stderr, "rank: one ruler pass covered %llu of %u chains, ranking again\n",
-                        (unsigned long long)hsc.nvisited, Ma);
-            rank_async = false;
-            // (the look-back compaction's LH: super index per node, at heads the head -> index map)
-            EC_CHECK(rank_supers(s, Ma, N, nr, rounds, false, async_LH));  // (PathOf reads the new PKs / RKs)
-            s->stats.n_rulers = nr;
-            EC_CHECK(starts_pass());
-        }
-    }
-    if (rounds) {
-        unsigned int used = 1;
-        for (int r = 0; r < rounds; r++)
-            if (hsc.active[r]) used = r + 2;
-        s->stats.rank_rounds = std::min<unsigned int>(used, rounds);
-        if (hsc.active[rounds - 1] != 0) {
-            set_error("ruler list ranking did not converge in %d rounds", rounds);
-            return EC_ERR_STATE;
-        }
-    }
-    unsigned int nc = hsc.nstarts;
-    unsigned int nsort = nc;
-    if (nx) {  // all_contigs on the components with one-way links, their starts after the others
-        EC_CHECK(s->x_done.ensure(Nn));
-        EC_CHECK(s->x_len.ensure((size_t)nx * 4));
-        EC_CHECK(s->x_m.ensure((size_t)nx * 4));
-        EC_CHECK(s->x_cid.ensure((size_t)nx * 4));
-        EC_HIP(hipMemsetAsync(s->x_done.p, 0, Nn, st));
-        k_x_emulate<<<grid_for(nx, 64), 64, 0, st>>>(
-            s->x_lv.as<unsigned int>(), nx, s->x_par.as<unsigned int>(), s->upal.as<uint8_t>(),
-            s->x_succ.as<unsigned int>(), s->dkey.as<K128>(), k, N, s->dfc.as<unsigned long long>(),
-            s->dft.as<unsigned long long>(), s->x_done.as<uint8_t>(), s->skeys.as<unsigned long long>() + nc,
-            s->svals.as<unsigned int>() + nc, s->x_len.as<unsigned int>(), s->x_m.as<unsigned int>(), &dsc->nxs,
-            &dsc->xbad);
-        unsigned int xs[2] = {0, 0};
-        EC_CHECK(d2h(s, xs, &dsc->nxs, 8, st));
-        EC_CHECK(host_sync(s, st));
-        if (xs[1]) {
-            set_error("a contig walk enters a cycle without its start: the reference's get_contig_forward "
-                      "(referenceAssembler.py:59-77) never returns on this input");
-            return EC_ERR_STATE;
-        }
-        nsort = nc + nx;  // (the emulation's non-starts carry key NONE: sorted past the starts)
-        nc += xs[0];
-    }
-    s->stats.n_contigs = nc;
-    EC_CHECK(s->cwalk.ensure((size_t)std::max(nc, 1u) * sizeof(Walk)));
-    EC_CHECK(s->coff.ensure((size_t)(nc + 1) * 8));
-    EC_CHECK(s->ewalk.ensure((size_t)std::max(nc, 1u) * sizeof(EWalk)));
-    // few starts: order, walks, offsets and emission records in one workgroup (k_starts_small)
-    const bool small = !nx && nc && nc <= SMALL_STARTS && !kn().no_small_starts;
-    if (small)
-        k_starts_small<<<1, SMALL_STARTS_NT, 0, st>>>(
-            s->skeys.as<unsigned long long>(), s->svals.as<unsigned int>(), nc, s->upal.as<uint8_t>(),
-            P, s->PL.as<unsigned int>(), k,
-            s->svals2.as<unsigned int>(), s->cidxOf.as<unsigned int>(), s->coff.as<unsigned long long>(),
-            s->cwalk.as<Walk>(), s->ewalk.as<EWalk>());
-    if (nsort && !small)
-        EC_CHECK(sort_pairs(s, s->skeys.as<unsigned long long>(), s->skeys2.as<unsigned long long>(),
-                            s->svals.as<unsigned int>(), s->svals2.as<unsigned int>(), nsort));
-    const unsigned int *sorted_nodes = s->svals2.as<unsigned int>();
-    if (!small) {
-    EC_CHECK(s->clen.ensure((size_t)(nc + 1) * 8));
-    EC_HIP(hipMemsetAsync(s->clen.p, 0, (size_t)(nc + 1) * 8, st));
-    if (nc) {
-        k_contig_len<<<grid_for(nc, B), B, 0, st>>>(s->upal.as<uint8_t>(), P, s->PL.as<unsigned int>(), sorted_nodes, nc,
-                                                   k, s->cidxOf.as<unsigned int>(), s->clen.as<unsigned long long>(),
-                                                   s->cwalk.as<Walk>(), nx ? s->x_len.as<unsigned int>() : nullptr,
-                                                   nx ? s->x_cid.as<unsigned int>() : nullptr);
-    }
-    EC_CHECK(scan_u64(s, s->clen.as<unsigned long long>(), s->coff.as<unsigned long long>(), nc + 1));
-    }
-    // the total travels with the other results (no round trip here): the character buffer is
-    // sized for the bound 2U + nc (k - 1) (a walk covers at most its path; a self-twin path's
-    // nodes are up to twice its canonical k-mers)
-    // (few contigs: k_links_small's result block carries the offsets and the total)
-    EC_CHECK(s->h_coff.resize(nc + 1));
-    if (!small) EC_CHECK(d2h(s, &s->h_coff[nc], s->coff.as<unsigned long long>() + nc, 8, st));
-    // the results' copies to host memory run on the output stream, each as soon as its data is
-    // final: the contig offsets here (overlapping emission and GFA), the characters after the
-    // emission, the link offsets after the GFA counts (ecoli10m_err: 1.1 M contigs, 47 MB of
-    // results copied after GFA took ~1 ms in line)
-    auto ostream_ready = [&]() -> int {
-        if (!s->ostream) EC_HIP(hipStreamCreateWithFlags(&s->ostream, hipStreamNonBlocking));
-        for (auto &e : s->oev)
-            if (!e) EC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        return EC_OK;
-    };
-    // (only for many contigs: the event / stream-wait / copy calls cost the host ~30 us, more
-    // than the headline's few bytes of offsets and link counts take in line)
-    const bool ocopy = nc >= OCOPY_MIN;
-    EC_CHECK(ostream_ready());
-    if (ocopy) {
-        EC_HIP(hipEventRecord(s->oev[2], st));
-        EC_HIP(hipStreamWaitEvent(s->ostream, s->oev[2], 0));
-        EC_HIP(hipMemcpyAsync(s->h_coff.data(), s->coff.p, (size_t)nc * 8, hipMemcpyDeviceToHost, s->ostream));
-    }
-    mark(s, 2 * EC_STAGE_STARTS + 1);
-    uint64_t chars_bound = 2ull * U + (uint64_t)nc * (uint64_t)(k - 1);
-    if (nx) {  // emulated contigs may overlap: the bound is their exact total
-        unsigned long long tot = 0;
-        EC_CHECK(d2h(s, &tot, s->coff.as<unsigned long long>() + nc, 8, st));
-        EC_CHECK(host_sync(s, st));
-        chars_bound = std::max<uint64_t>(chars_bound, tot);
-    }
+}
 
-    // ---- emit -----------------------------------------------------------------------------
-    mark(s, 2 * EC_STAGE_EMIT);
-    EC_CHECK(s->chars.ensure(std::max<size_t>(chars_bound, 1) + 16));  // (+16: k_pack_chars reads 16 at a time)
-    EC_CHECK(s->cfirst.ensure((size_t)std::max(nc, 1u) * 4));
-    EC_CHECK(s->clast.ensure((size_t)std::max(nc, 1u) * 4));
-    if (nc && !small)
-        k_ewalk<<<grid_for(nc, B), B, 0, st>>>(s->cwalk.as<Walk>(), s->coff.as<unsigned long long>(), nc,
-                                              s->ewalk.as<EWalk>());
-    if (U)
-        k_emit<Ops><<<grid_for(N, B), B, 0, st>>>(s->upal.as<uint8_t>(), P,
-                                            s->PL.as<unsigned int>(), s->dkey.as<typename Ops::K>(),
-                                            s->cidxOf.as<unsigned int>(), s->ewalk.as<EWalk>(),
-                                            N, k, s->chars.as<char>(), std::max<uint64_t>(chars_bound, 1),
-                                            s->cfirst.as<unsigned int>(), s->clast.as<unsigned int>(),
-                                            s->headOf.as<unsigned int>(), s->tailOf.as<unsigned int>(), &dsc->skew);
-    if constexpr (XT) {
-        if (nx) {
-            EC_CHECK(s->x_head.ensure(Nn * 4));
-            EC_CHECK(s->x_tail.ensure(Nn * 4));
-            EC_HIP(hipMemsetAsync(s->x_head.p, 0, Nn * 4, st));
-            EC_HIP(hipMemsetAsync(s->x_tail.p, 0, Nn * 4, st));
-            k_x_emit<<<grid_for(nx, B), B, 0, st>>>(
-                s->x_lv.as<unsigned int>(), s->x_len.as<unsigned int>(), s->x_m.as<unsigned int>(),
-                s->x_cid.as<unsigned int>(), s->skeys.as<unsigned long long>() + hsc.nstarts, nx, s->upal.as<uint8_t>(),
-                s->x_succ.as<unsigned int>(), s->dkey.as<K128>(), k, s->coff.as<unsigned long long>(),
-                s->chars.as<char>(), s->cfirst.as<unsigned int>(), s->clast.as<unsigned int>(),
-                s->x_head.as<unsigned int>(), s->x_tail.as<unsigned int>());
-            k_x_heads<<<grid_for(N, B), B, 0, st>>>(N, s->x_head.as<unsigned int>(), s->x_tail.as<unsigned int>(),
-                                                    s->headOf.as<unsigned int>(), s->tailOf.as<unsigned int>());
-        }
-    }
-    // the characters' copy to host memory starts on the output stream as soon as the emission is
-    // done, sized by the previous call's total (a stream of equal batches, the bench's steps): it
-    // overlaps GFA and the link compaction instead of following a read-back of the total; a
-    // larger total is copied again in full after the read-back
-    // standard alphabet: the characters travel as 2-bit codes (a quarter of the PCIe bytes)
-    const bool pack = !XT && kn().no_char_pack == 0;
-    const void *csrc = s->chars.p;
-    if (pack) {
-        const uint64_t cap16 = (std::max<uint64_t>(chars_bound, 1) + 15) / 16;
-        EC_CHECK(s->dchars.ensure(cap16 * 4));
-        k_pack_chars<<<std::min(grid_for(cap16, B), 8192u), B, 0, st>>>(
-            s->chars.as<uint4>(), s->coff.as<unsigned long long>() + nc, cap16, s->dchars.as<uint32_t>());
-        csrc = s->dchars.p;
-    }
-    auto hbytes = [&](uint64_t n) { return pack ? (n + 3) / 4 : n; };  // host bytes of n characters
-    uint64_t pre = 0;
-    if (s->last_nchars && s->last_nchars <= chars_bound && kn().no_spec == 0) {
-        pre = s->last_nchars;
-        EC_CHECK(s->h_chars.resize(hbytes(pre)));
-        EC_HIP(hipEventRecord(s->oev[0], st));
-        EC_HIP(hipStreamWaitEvent(s->ostream, s->oev[0], 0));
-        EC_HIP(hipMemcpyAsync(s->h_chars.data(), csrc, hbytes(pre), hipMemcpyDeviceToHost, s->ostream));
-        EC_HIP(hipEventRecord(s->oev[1], s->ostream));
-    }
-    s->last_nchars = 0;
-    mark(s, 2 * EC_STAGE_EMIT + 1);
+// the output stream and its events (ec_session::oev), created on first use
+int ostream_ready(ec_session *s) {
+    if (!s->ostream) EC_HIP(hipStreamCreateWithFlags(&s->ostream, hipStreamNonBlocking));
+    for (auto &e : s->oev)
+        if (!e) EC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return EC_OK;
+}
 
-    // ---- GFA ------------------------------------------------------------------------------
-    mark(s, 2 * EC_STAGE_GFA);
-    EC_CHECK(s->lk.ensure((size_t)std::max(nc, 1u) * 16 * 8));
-    EC_CHECK(s->lcnt.ensure((size_t)std::max(nc, 1u) * 2 * 4));
-    if (nc)
-        k_gfa<Ops, Index><<<grid_for(nc, B), B, 0, st>>>(sidx, s->dkey.as<typename Ops::K>(),
-                                            s->upal.as<uint8_t>(), s->cfirst.as<unsigned int>(),
-                                            s->clast.as<unsigned int>(), s->headOf.as<unsigned int>(),
-                                            s->tailOf.as<unsigned int>(), nc, k, s->lk.as<long long>(),
-                                            s->lcnt.as<unsigned int>());
-    mark(s, 2 * EC_STAGE_GFA + 1);
+// host bytes of n contig characters (packed: 2-bit codes, 4 a byte)
+inline uint64_t char_bytes(bool pack, uint64_t n) { return pack ? (n + 3) / 4 : n; }
 
-    // ---- results to host (links compacted on the device: only the used entries travel) -----
+// results to host (links compacted on the device: only the used entries travel): the link
+// counts, offsets and total -- few contigs: one block with the contig offsets -- the bound checks
+// on the characters, then what the first round trip sized: characters past the early copy's pre
+// (from csrc, packed or not) and the compacted links
+int results_to_host(ec_session *s, unsigned int nc, bool small, bool ocopy, uint64_t chars_bound, bool pack,
+                    const void *csrc, uint64_t pre) {
+    hipStream_t st = s->stream;
+    const unsigned B = 256;
+    Scalars *dsc = s->scal.as<Scalars>();
     const unsigned int n2 = 2 * nc;
     s->links_compact = true;
     EC_CHECK(s->h_lc8.resize(n2));
@@ -3485,11 +2930,11 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
         return EC_ERR_STATE;
     }
     if (pre && nchars > pre) EC_HIP(hipEventSynchronize(s->oev[1]));  // (before h_chars may move)
-    EC_CHECK(s->h_chars.resize(hbytes(nchars)));
+    EC_CHECK(s->h_chars.resize(char_bytes(pack, nchars)));
     s->chars_packed = pack;
     s->nchars_host = nchars;
     bool again = nchars > pre;  // (a second round trip: characters or links still to copy)
-    if (nchars > pre) EC_CHECK(d2h(s, s->h_chars.data(), csrc, hbytes(nchars), st));
+    if (nchars > pre) EC_CHECK(d2h(s, s->h_chars.data(), csrc, char_bytes(pack, nchars), st));
     const uint64_t nlinks = nlinks64;
     EC_CHECK(s->h_links32.resize(nlinks));  // (small: the copied bound's first nlinks stay)
     if (nlinks && !small) {
@@ -3504,6 +2949,245 @@ int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const u
     if (ocopy || pre) EC_HIP(hipStreamSynchronize(s->ostream));  // (offsets, characters, link counts)
     s->last_nchars = nchars;
     s->stats.n_links = nlinks;
+    return EC_OK;
+}
+
+// all_contigs:79-111 on the device from the solid set of phase_count / phase_merge
+template <typename Ops, typename Index>
+int phase_graph(ec_session *s, int k, unsigned int U, const Index &sidx, const unsigned int *ext_succ = nullptr) {
+    hipStream_t st = s->stream;
+    const unsigned B = 256;
+    Scalars *dsc = s->scal.as<Scalars>();
+    Scalars hsc{};
+    const unsigned int N = 2 * U;
+    const size_t Nn = std::max<size_t>(N, 1);
+    // list ranking by tile contraction (rank_tile.h) on minimizer-local ids, the node-level
+    // ruling set otherwise (EULERHIP_RANK=1 / 2 force one or the other); tile ranking needs
+    // neither pred nor the node walk records
+    const bool tile_rank = kn().rank == 2 || (kn().rank != 1 && ids_minimizer_local(sidx));
+    constexpr bool XT = std::is_same<Ops, OpsX>::value;  // extended alphabet (extended.h)
+
+    // ---- links ----------------------------------------------------------------------------
+    mark(s, 2 * EC_STAGE_LINKS);
+    unsigned int nx = 0;  // extended alphabet: dict entries of components with one-way links
+    EC_CHECK((graph_links<Ops, Index>(s, k, U, sidx, ext_succ, tile_rank, nx)));
+    mark(s, 2 * EC_STAGE_LINKS + 1);
+
+    // ---- rank (sparse ruling set + weighted Wyllie on the rulers) -------------------------
+    mark(s, 2 * EC_STAGE_RANK);
+    EC_CHECK(s->rid.ensure(Nn * 8));  // (ruler, offset) per node
+    EC_CHECK(s->rlist.ensure(Nn * 4));
+    EC_CHECK(s->rbc.ensure(((Nn + RULER_CHUNK - 1) / RULER_CHUNK) * 8));
+    EC_CHECK(s->nextR.ensure(Nn * 4));
+    EC_CHECK(s->st0.ensure(Nn * sizeof(RJump)));
+    EC_CHECK(s->st1.ensure(Nn * sizeof(RJump)));
+    EC_CHECK(s->PK.ensure(Nn * 4));
+    EC_CHECK(s->RK.ensure(Nn * 4));
+    EC_CHECK(s->PL.ensure(Nn * 4));
+    EC_CHECK(s->PM.ensure(Nn * 8));
+    Ranked rk;
+    s->stats.rank_rounds = 0;
+    if (U && tile_rank) EC_CHECK(rank_tiles(s, U, sidx, rk));
+    if (U && !tile_rank) EC_CHECK(rank_nodes(s, U, rk.nr, rk.rounds));
+    s->stats.n_rulers = rk.nr;
+    mark(s, 2 * EC_STAGE_RANK + 1);
+
+    // ---- starts + order -------------------------------------------------------------------
+    const PathOf P = rk.chain_paths ? PathOf{s->PK.as<unsigned int>(), s->RK.as<unsigned int>(), rk.LH, rk.LR,
+                                             s->rt_pks.as<unsigned int>(), s->rt_rks.as<unsigned int>()}
+                                    : path_of(s->PK.as<unsigned int>(), s->RK.as<unsigned int>());
+    mark(s, 2 * EC_STAGE_STARTS);
+    EC_CHECK(s->cidxOf.ensure(Nn * 4));
+    EC_CHECK(s->skeys.ensure(Nn * 8));
+    EC_CHECK(s->svals.ensure(Nn * 4));
+    EC_CHECK(s->skeys2.ensure(Nn * 8));
+    EC_CHECK(s->svals2.ensure(Nn * 4));
+    // the emission's node maps are cleared behind the starts' read-back copy (below): the device
+    // works through the fills while the host wakes up; the start kernels read none of them
+    EC_CHECK(s->headOf.ensure(Nn * 4));
+    EC_CHECK(s->tailOf.ensure(Nn * 4));
+    EC_CHECK(starts_pass(s, U, P, nx, hsc));
+    if (rk.async) {  // the asynchronous ranking's checks, on the scalars the starts read back
+        const unsigned int Ma = (unsigned int)hsc.chains;
+        rk.nr = hsc.nr;
+        s->stats.n_rulers = rk.nr;
+        if (kn().verbose)
+            fprintf(stderr, "rank: %u oriented nodes, %u chains (tile contraction), %u rulers, %llu visited\n", N, Ma,
+                    rk.nr, (unsigned long long)hsc.nvisited);
+        if (Ma) note_rounds(s, hsc, rk.rounds);
+        if (hsc.nvisited != Ma || (Ma && hsc.active[rk.rounds - 1] != 0)) {
+            // a cycle of chains no ruler reached (or unconverged rounds): the ranking with its
+            // host-checked ruler passes, then the starts again
+            if (kn().verbose)
+                fprintf(stderr, "rank: one ruler pass covered %llu of %u chains, ranking again\n",
+                        (unsigned long long)hsc.nvisited, Ma);
+            rk.async = false;
+            // (the look-back compaction's LH: super index per node, at heads the head -> index map)
+            EC_CHECK(rank_supers(s, Ma, N, rk.nr, rk.rounds, false, rk.LH));  // (PathOf reads the new PKs / RKs)
+            s->stats.n_rulers = rk.nr;
+            EC_CHECK(starts_pass(s, U, P, nx, hsc));
+        }
+    }
+    if (rk.rounds) {
+        unsigned int used = 1;
+        for (int r = 0; r < rk.rounds; r++)
+            if (hsc.active[r]) used = r + 2;
+        s->stats.rank_rounds = std::min<unsigned int>(used, rk.rounds);
+        if (hsc.active[rk.rounds - 1] != 0) {
+            set_error("ruler list ranking did not converge in %d rounds", rk.rounds);
+            return EC_ERR_STATE;
+        }
+    }
+    unsigned int nc = hsc.nstarts;
+    unsigned int nsort = nc;
+    if (nx) {  // all_contigs on the components with one-way links, their starts after the others
+        EC_CHECK(s->x_done.ensure(Nn));
+        EC_CHECK(s->x_len.ensure((size_t)nx * 4));
+        EC_CHECK(s->x_m.ensure((size_t)nx * 4));
+        EC_CHECK(s->x_cid.ensure((size_t)nx * 4));
+        EC_HIP(hipMemsetAsync(s->x_done.p, 0, Nn, st));
+        k_x_emulate<<<grid_for(nx, 64), 64, 0, st>>>(
+            s->x_lv.as<unsigned int>(), nx, s->x_par.as<unsigned int>(), s->upal.as<uint8_t>(),
+            s->x_succ.as<unsigned int>(), s->dkey.as<K128>(), k, N, s->dfc.as<unsigned long long>(),
+            s->dft.as<unsigned long long>(), s->x_done.as<uint8_t>(), s->skeys.as<unsigned long long>() + nc,
+            s->svals.as<unsigned int>() + nc, s->x_len.as<unsigned int>(), s->x_m.as<unsigned int>(), &dsc->nxs,
+            &dsc->xbad);
+        unsigned int xs[2] = {0, 0};
+        EC_CHECK(d2h(s, xs, &dsc->nxs, 8, st));
+        EC_CHECK(host_sync(s, st));
+        if (xs[1]) {
+            set_error("a contig walk enters a cycle without its start: the reference's get_contig_forward "
+                      "(referenceAssembler.py:59-77) never returns on this input");
+            return EC_ERR_STATE;
+        }
+        nsort = nc + nx;  // (the emulation's non-starts carry key NONE: sorted past the starts)
+        nc += xs[0];
+    }
+    s->stats.n_contigs = nc;
+    EC_CHECK(s->cwalk.ensure((size_t)std::max(nc, 1u) * sizeof(Walk)));
+    EC_CHECK(s->coff.ensure((size_t)(nc + 1) * 8));
+    EC_CHECK(s->ewalk.ensure((size_t)std::max(nc, 1u) * sizeof(EWalk)));
+    // few starts: order, walks, offsets and emission records in one workgroup (k_starts_small)
+    const bool small = !nx && nc && nc <= SMALL_STARTS && !kn().no_small_starts;
+    if (small)
+        k_starts_small<<<1, SMALL_STARTS_NT, 0, st>>>(
+            s->skeys.as<unsigned long long>(), s->svals.as<unsigned int>(), nc, s->upal.as<uint8_t>(),
+            P, s->PL.as<unsigned int>(), k,
+            s->svals2.as<unsigned int>(), s->cidxOf.as<unsigned int>(), s->coff.as<unsigned long long>(),
+            s->cwalk.as<Walk>(), s->ewalk.as<EWalk>());
+    if (nsort && !small)
+        EC_CHECK(sort_pairs(s, s->skeys.as<unsigned long long>(), s->skeys2.as<unsigned long long>(),
+                            s->svals.as<unsigned int>(), s->svals2.as<unsigned int>(), nsort));
+    const unsigned int *sorted_nodes = s->svals2.as<unsigned int>();
+    if (!small) {
+        EC_CHECK(s->clen.ensure((size_t)(nc + 1) * 8));
+        EC_HIP(hipMemsetAsync(s->clen.p, 0, (size_t)(nc + 1) * 8, st));
+        if (nc)
+            k_contig_len<<<grid_for(nc, B), B, 0, st>>>(
+                s->upal.as<uint8_t>(), P, s->PL.as<unsigned int>(), sorted_nodes, nc, k, s->cidxOf.as<unsigned int>(),
+                s->clen.as<unsigned long long>(), s->cwalk.as<Walk>(), nx ? s->x_len.as<unsigned int>() : nullptr,
+                nx ? s->x_cid.as<unsigned int>() : nullptr);
+        EC_CHECK(scan_u64(s, s->clen.as<unsigned long long>(), s->coff.as<unsigned long long>(), nc + 1));
+    }
+    // the total travels with the other results (no round trip here): the character buffer is
+    // sized for the bound 2U + nc (k - 1) (a walk covers at most its path; a self-twin path's
+    // nodes are up to twice its canonical k-mers)
+    // (few contigs: k_links_small's result block carries the offsets and the total)
+    EC_CHECK(s->h_coff.resize(nc + 1));
+    if (!small) EC_CHECK(d2h(s, &s->h_coff[nc], s->coff.as<unsigned long long>() + nc, 8, st));
+    // the results' copies to host memory run on the output stream, each as soon as its data is
+    // final: the contig offsets here (overlapping emission and GFA), the characters after the
+    // emission, the link offsets after the GFA counts (ecoli10m_err: 1.1 M contigs, 47 MB of
+    // results copied after GFA took ~1 ms in line)
+    // (only for many contigs: the event / stream-wait / copy calls cost the host ~30 us, more
+    // than the headline's few bytes of offsets and link counts take in line)
+    const bool ocopy = nc >= OCOPY_MIN;
+    EC_CHECK(ostream_ready(s));
+    if (ocopy) {
+        EC_HIP(hipEventRecord(s->oev[2], st));
+        EC_HIP(hipStreamWaitEvent(s->ostream, s->oev[2], 0));
+        EC_HIP(hipMemcpyAsync(s->h_coff.data(), s->coff.p, (size_t)nc * 8, hipMemcpyDeviceToHost, s->ostream));
+    }
+    mark(s, 2 * EC_STAGE_STARTS + 1);
+    uint64_t chars_bound = 2ull * U + (uint64_t)nc * (uint64_t)(k - 1);
+    if (nx) {  // emulated contigs may overlap: the bound is their exact total
+        unsigned long long tot = 0;
+        EC_CHECK(d2h(s, &tot, s->coff.as<unsigned long long>() + nc, 8, st));
+        EC_CHECK(host_sync(s, st));
+        chars_bound = std::max<uint64_t>(chars_bound, tot);
+    }
+
+    // ---- emit -----------------------------------------------------------------------------
+    mark(s, 2 * EC_STAGE_EMIT);
+    EC_CHECK(s->chars.ensure(std::max<size_t>(chars_bound, 1) + 16));  // (+16: k_pack_chars reads 16 at a time)
+    EC_CHECK(s->cfirst.ensure((size_t)std::max(nc, 1u) * 4));
+    EC_CHECK(s->clast.ensure((size_t)std::max(nc, 1u) * 4));
+    if (nc && !small)
+        k_ewalk<<<grid_for(nc, B), B, 0, st>>>(s->cwalk.as<Walk>(), s->coff.as<unsigned long long>(), nc,
+                                              s->ewalk.as<EWalk>());
+    if (U)
+        k_emit<Ops><<<grid_for(N, B), B, 0, st>>>(s->upal.as<uint8_t>(), P,
+                                            s->PL.as<unsigned int>(), s->dkey.as<typename Ops::K>(),
+                                            s->cidxOf.as<unsigned int>(), s->ewalk.as<EWalk>(),
+                                            N, k, s->chars.as<char>(), std::max<uint64_t>(chars_bound, 1),
+                                            s->cfirst.as<unsigned int>(), s->clast.as<unsigned int>(),
+                                            s->headOf.as<unsigned int>(), s->tailOf.as<unsigned int>(), &dsc->skew);
+    if constexpr (XT) {
+        if (nx) {
+            EC_CHECK(s->x_head.ensure(Nn * 4));
+            EC_CHECK(s->x_tail.ensure(Nn * 4));
+            EC_HIP(hipMemsetAsync(s->x_head.p, 0, Nn * 4, st));
+            EC_HIP(hipMemsetAsync(s->x_tail.p, 0, Nn * 4, st));
+            k_x_emit<<<grid_for(nx, B), B, 0, st>>>(
+                s->x_lv.as<unsigned int>(), s->x_len.as<unsigned int>(), s->x_m.as<unsigned int>(),
+                s->x_cid.as<unsigned int>(), s->skeys.as<unsigned long long>() + hsc.nstarts, nx, s->upal.as<uint8_t>(),
+                s->x_succ.as<unsigned int>(), s->dkey.as<K128>(), k, s->coff.as<unsigned long long>(),
+                s->chars.as<char>(), s->cfirst.as<unsigned int>(), s->clast.as<unsigned int>(),
+                s->x_head.as<unsigned int>(), s->x_tail.as<unsigned int>());
+            k_x_heads<<<grid_for(N, B), B, 0, st>>>(N, s->x_head.as<unsigned int>(), s->x_tail.as<unsigned int>(),
+                                                    s->headOf.as<unsigned int>(), s->tailOf.as<unsigned int>());
+        }
+    }
+    // the characters' copy to host memory starts on the output stream as soon as the emission is
+    // done, sized by the previous call's total (a stream of equal batches, the bench's steps): it
+    // overlaps GFA and the link compaction instead of following a read-back of the total; a
+    // larger total is copied again in full after the read-back
+    // standard alphabet: the characters travel as 2-bit codes (a quarter of the PCIe bytes)
+    const bool pack = !XT && kn().no_char_pack == 0;
+    const void *csrc = s->chars.p;
+    if (pack) {
+        const uint64_t cap16 = (std::max<uint64_t>(chars_bound, 1) + 15) / 16;
+        EC_CHECK(s->dchars.ensure(cap16 * 4));
+        k_pack_chars<<<std::min(grid_for(cap16, B), 8192u), B, 0, st>>>(
+            s->chars.as<uint4>(), s->coff.as<unsigned long long>() + nc, cap16, s->dchars.as<uint32_t>());
+        csrc = s->dchars.p;
+    }
+    uint64_t pre = 0;
+    if (s->last_nchars && s->last_nchars <= chars_bound && kn().no_spec == 0) {
+        pre = s->last_nchars;
+        EC_CHECK(s->h_chars.resize(char_bytes(pack, pre)));
+        EC_HIP(hipEventRecord(s->oev[0], st));
+        EC_HIP(hipStreamWaitEvent(s->ostream, s->oev[0], 0));
+        EC_HIP(hipMemcpyAsync(s->h_chars.data(), csrc, char_bytes(pack, pre), hipMemcpyDeviceToHost, s->ostream));
+        EC_HIP(hipEventRecord(s->oev[1], s->ostream));
+    }
+    s->last_nchars = 0;
+    mark(s, 2 * EC_STAGE_EMIT + 1);
+
+    // ---- GFA ------------------------------------------------------------------------------
+    mark(s, 2 * EC_STAGE_GFA);
+    EC_CHECK(s->lk.ensure((size_t)std::max(nc, 1u) * 16 * 8));
+    EC_CHECK(s->lcnt.ensure((size_t)std::max(nc, 1u) * 2 * 4));
+    if (nc)
+        k_gfa<Ops, Index><<<grid_for(nc, B), B, 0, st>>>(sidx, s->dkey.as<typename Ops::K>(),
+                                            s->upal.as<uint8_t>(), s->cfirst.as<unsigned int>(),
+                                            s->clast.as<unsigned int>(), s->headOf.as<unsigned int>(),
+                                            s->tailOf.as<unsigned int>(), nc, k, s->lk.as<long long>(),
+                                            s->lcnt.as<unsigned int>());
+    mark(s, 2 * EC_STAGE_GFA + 1);
+
+    // ---- results to host -------------------------------------------------------------------
+    EC_CHECK(results_to_host(s, nc, small, ocopy, chars_bound, pack, csrc, pre));
 
     s->stats.n_dict = 2ull * U - hsc.npal;  // len(build()): palindromes have one entry
 
@@ -4339,28 +4023,6 @@ static void unpack_codes(const uint8_t *codes, uint64_t n, char *out) {
     for (uint64_t c = 4 * full; c < n; c++) out[c] = "ACGT"[(codes[full] >> (2 * (c & 3))) & 3];
 }
 
-// every device buffer of a session (destroy, trim)
-template <typename Fn>
-static void for_each_buf(ec_session *s, Fn fn) {
-    DevBuf *all[] = {&s->h_reads, &s->h_offsets, &s->hll, &s->scal, &s->table, &s->dkey, &s->dcnt, &s->dfc, &s->dft,
-                     &s->upal, &s->outdeg, &s->cand, &s->succ, &s->pred, &s->st0, &s->st1, &s->startOf, &s->skeys,
-                     &s->svals, &s->skeys2, &s->svals2, &s->cidxOf, &s->clen, &s->coff, &s->chars, &s->cfirst,
-                     &s->clast, &s->headOf, &s->tailOf, &s->lk, &s->lcnt, &s->tmp, &s->dchars, &s->dcounts,
-                     &s->rid, &s->rlist, &s->nextR, &s->PK, &s->RK, &s->PL, &s->PM,
-                     &s->ocnt, &s->hist, &s->ftot, &s->cnt, &s->offs, &s->bstart, &s->tot, &s->recs, &s->recs2, &s->sub, &s->bnp, &s->rbc,
-                     &s->mbid, &s->mbid2, &s->midx, &s->midx2, &s->gcur, &s->cwalk, &s->ewalk, &s->lc8, &s->x_par, &s->x_irr,
-                     &s->x_in, &s->x_succ, &s->x_done, &s->x_lk, &s->x_lv, &s->x_lk2, &s->x_lv2, &s->x_len,
-                     &s->x_m, &s->x_cid, &s->x_head, &s->x_tail, &s->rt_tcnt, &s->rt_tbase, &s->rt_srec,
-                     &s->rt_snrec, &s->rt_sidx, &s->rt_pks, &s->rt_rks, &s->rt_hasp, &s->rt_lr, &s->wbv, &s->bmark, &s->rt_tb,
-                     &s->jrec, &s->joid, &s->jout, &s->jseg, &s->jcnt, &s->xrec,
-                     &s->skm_rec, &s->skm_ev, &s->skm_end, &s->wcodes_tab,
-                     &s->run_cnt, &s->run_ends, &s->run_dends, &s->rt_lb,
-                     &s->jl_kof, &s->jl_rs, &s->jl_re, &s->jl_cnt, &s->jl_off, &s->jl_flag, &s->jl_frec, &s->rpack,
-                     &s->clip_cand, &s->clip_list, &s->clip_kill, &s->clip_tot,
-                     &s->pop_key, &s->pop_sum, &s->pop_tcnt, &s->pop_toff, &s->pop_tile, &s->spec_hist};
-    for (auto *b : all) fn(*b);
-}
-
 extern "C" {
 
 int ec_session_create(ec_session **out, int device) {
@@ -4424,18 +4086,10 @@ int ec_session_trim(ec_session *s, uint64_t min_bytes) {
     // no device state survives: the next call starts from its inputs (results already copied to
     // host memory stay fetchable)
     // (whatever min_bytes released: a trim always drops the held records and emitted runs too)
-    drop_step_state(s);
+    drop_device_state(s, "ec_session_trim released the assembly's device state");
     s->n_dense = 0;
-    s->dense_ok = false;
-    s->clip_ok = false;
-    s->clip_why = "ec_session_trim released the assembly's device state";
-    s->own_valid = false;
-    s->bmark_ok = false;
-    s->seg_marks = 0;
     s->skspec.valid = false;
     s->jlspec.valid = s->jlspec.queued = false;  // (its capacities are those of released buffers)
-    s->graph_loaded = false;
-    s->placed = false;
     s->pipe.active = false;
     return EC_OK;
 }
@@ -4455,44 +4109,22 @@ int ec_session_destroy(ec_session *s) {
     if (s->stream) hipStreamSynchronize(s->stream);
     if (s->ostream) hipStreamSynchronize(s->ostream);
     if (s->cstream) hipStreamSynchronize(s->cstream);
-    for_each_buf(s, [](DevBuf &b) { b.release(); });
-    s->h_chars.release();
-    s->hmeta.release();
-    s->bounce.release();
-    s->pend.clear();
-    s->h_coff.release();
-    s->h_loff.release();
-    s->h_links.release();
-    s->h_lc8.release();
-    s->h_links32.release();
-    s->h_blk.release();
     if (s->events) {
         for (auto &e : s->ev) hipEventDestroy(e);
         for (auto &e : s->kev) hipEventDestroy(e);
     }
-    s->p_codes.release();
-    s->p_exc.release();
     if (s->rd_ev) hipEventDestroy(s->rd_ev);
-    if (s->ostream) {
-        hipStreamSynchronize(s->ostream);
-        hipStreamDestroy(s->ostream);
-    }
     for (auto &e : s->oev)
         if (e) hipEventDestroy(e);
     for (auto &e : s->pipe.ev) hipEventDestroy(e);
     for (auto &sl : s->stg) {
         for (auto &e : sl.pipe.ev) hipEventDestroy(e);
         if (sl.free_ev) hipEventDestroy(sl.free_ev);
-        sl.codes.release();
-        sl.exc.release();
-        sl.off.release();
     }
-    if (s->cstream) {
-        hipStreamSynchronize(s->cstream);
-        hipStreamDestroy(s->cstream);
-    }
+    if (s->ostream) hipStreamDestroy(s->ostream);
+    if (s->cstream) hipStreamDestroy(s->cstream);
     if (s->own_stream && s->stream) hipStreamDestroy(s->stream);
-    delete s;
+    delete s;  // (its device and pinned buffers free themselves: session.h)
     return EC_OK;
 }
 

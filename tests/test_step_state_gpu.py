@@ -283,12 +283,13 @@ def solid(data):
 
 # ---- a. refusal matrix ------------------------------------------------------------------------
 # consumer (its C entry point) -> (the legitimate sequence it belongs to, its step, the code the
-# header gives a late call).  The guard of every cell, in csrc/assemble.hip: each invalidator
-# clears the session flags the consumers test before their first HIP call --
+# header gives a late call).  The guard of every cell, in csrc/session.h and csrc/assemble.hip:
+# each invalidator clears the session flags the consumers test before their first HIP call --
 #   a new session       every flag at its default
-#   ec_session_trim     drop_step_state (hold, runs_ready, chain_scr, part_stage) + graph_loaded,
-#                       placed, dense_ok, n_dense, whatever min_bytes released
-#   ec_count_shard, ec_assemble_*   begin_call: drop_step_state + graph_loaded, placed, dense_ok
+#   ec_session_trim     drop_device_state: drop_step_state (hold, runs_ready, chain_scr,
+#                       part_stage) + graph_loaded, placed, dense_ok; then n_dense, whatever
+#                       min_bytes released
+#   ec_count_shard, ec_assemble_*   begin_call: the same drop_device_state
 #                       (the count sets dense_ok again)
 #   ec_graph_load       begin_call, then graph_loaded alone
 #   ec_graph_place      graph_place: drop_step_state + dense_ok, then graph_loaded and placed
