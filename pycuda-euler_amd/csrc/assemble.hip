@@ -380,14 +380,19 @@ BucketPlan plan_buckets(double est, long long limit) {
 // the partition checks the input and counts the windows; *invalid = the input does not meet
 // the prescan's conditions (the caller then takes the prescan path).
 // workgroups of k_skpart_w<npf, w, val> the device runs at once (CUs x resident per CU)
-static uint64_t skpart_slots(int npf, int w, bool val) {
-    static thread_local int cache[3][SK_W_MAX + 1][2] = {};
+// (n17: the W = 17 form that keeps 17-window runs whole, count_sk2.h sk2_nmax)
+static uint64_t skpart_slots(int npf, int w, bool val, bool n17) {
+    static thread_local int cache[3][SK_W_MAX + 2][2] = {};
     const int ni = npf == 4 ? 0 : npf == 7 ? 1 : 2;
-    int &c = cache[ni][w][val];
+    int &c = cache[ni][n17 ? SK_W_MAX + 1 : w][val];
     if (!c) {
         const void *fn = nullptr;
+#define EC_SKF17(NPF) \
+    if (n17 && npf == NPF) fn = val ? (const void *)&k_skpart_w<NPF, 17, true, true> : (const void *)&k_skpart_w<NPF, 17, false, true>;
+        EC_SKF17(4) EC_SKF17(7) EC_SKF17(10)
+#undef EC_SKF17
 #define EC_SKF(NPF, W)                                                                                        \
-    if (npf == NPF && w == W) fn = val ? (const void *)&k_skpart_w<NPF, W, true> : (const void *)&k_skpart_w<NPF, W, false>;
+    if (!n17 && npf == NPF && w == W) fn = val ? (const void *)&k_skpart_w<NPF, W, true> : (const void *)&k_skpart_w<NPF, W, false>;
 #define EC_SKF_W(W) EC_SKF(4, W) EC_SKF(7, W) EC_SKF(10, W)
         EC_SKF_W(7) EC_SKF_W(8) EC_SKF_W(9) EC_SKF_W(10) EC_SKF_W(11) EC_SKF_W(12)
         EC_SKF_W(13) EC_SKF_W(14) EC_SKF_W(15) EC_SKF_W(16) EC_SKF_W(17) EC_SKF_W(18)
@@ -409,11 +414,13 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
                     bool *invalid = nullptr) {
     done = false;
     if (invalid) *invalid = false;
+    // k = 31 on reads of M <= 128 windows: 17-window runs stay whole (the entry has the bit)
+    const bool n17 = k - SK_M + 1 == 17 && M <= SK2_FW17_MAXM;
     if (k >= SK_MIN_K && k <= 32) {
         // read groups: a multiple of the workgroups resident at once when there are more tiles
         // than that (2030 groups of 77 tiles on 768 slots ran 2.64 waves of workgroups, the last
         // one a third idle; 1536 of 102 tiles run 2 full ones), at most RF_MAX_RUNS (k_skrefine)
-        const uint64_t ntiles = (nreads + 63) / 64, slots = skpart_slots(npf, k - SK_M + 1, validate);
+        const uint64_t ntiles = (nreads + 63) / 64, slots = skpart_slots(npf, k - SK_M + 1, validate, n17);
         uint64_t g = std::max<uint64_t>(1, std::min<uint64_t>(ntiles, RF_MAX_RUNS));
         if (g > slots) g = g / slots * slots;
         gsize = ((ntiles + g - 1) / g) * 64;
@@ -457,7 +464,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
     mark(s, 2 * EC_STAGE_COUNT);
     kmark(s, 1, 0);
 #define EC_SKPART_WV(NPF, W, VAL)                                                                             \
-    k_skpart_w<NPF, W, VAL><<<lgb - lga, PT_THREADS, 0, st>>>(                                                   \
+    k_skpart_w<NPF, W, VAL, W == 17 && N17><<<lgb - lga, PT_THREADS, 0, st>>>(                                   \
         d_reads, d_off, nreads, mc, M, gsize, (uint32_t)G, cap, smask, recs, s->cnt.as<unsigned int>(),          \
         s->hll.as<uint8_t>(), &dsc->nrec, &dsc->overflow, &dsc->lens[2], &dsc->npos, lga, elim)
 #define EC_SKPART_W(NPF, W)            \
@@ -485,6 +492,7 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
         EC_CHECK(pipe_upto(s, pc));
       }
       {
+        constexpr bool N17 = false;  // (shadowed where case 17 takes the 17-window form)
         switch (mc.w) {
             case 7: EC_SKPART_NPF(7); break;
             case 8: EC_SKPART_NPF(8); break;
@@ -496,7 +504,14 @@ int phase_count_sk2(ec_session *s, const uint8_t *d_reads, const uint64_t *d_off
             case 14: EC_SKPART_NPF(14); break;
             case 15: EC_SKPART_NPF(15); break;
             case 16: EC_SKPART_NPF(16); break;
-            case 17: EC_SKPART_NPF(17); break;
+            case 17:
+                if (n17) {
+                    constexpr bool N17 = true;
+                    EC_SKPART_NPF(17);
+                } else {
+                    EC_SKPART_NPF(17);
+                }
+                break;
             default: EC_SKPART_NPF(18); break;  // k = 32
         }
       }

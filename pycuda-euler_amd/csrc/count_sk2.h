@@ -6,7 +6,7 @@
 // share their minimizer (superkmer.h: the smallest hash over the window's canonical m-mers,
 // the same for a k-mer and its twin) form a super-k-mer; all its k-mers belong to the
 // minimizer's bucket, so the run travels as ONE 16-byte record holding its L = n + k - 1
-// bases (2 bits each, n <= 16 windows) -- about (w + 1) / 2 windows per record:
+// bases (2 bits each, L <= 47, n <= 17 windows) -- about (w + 1) / 2 windows per record:
 //
 //   k_skpart    per read group : lane = read; m-mer hashes and van Herk / Gil-Werman sliding
 //                                minima (block length w, LDS ring), runs of equal minimizer
@@ -23,14 +23,17 @@
 //   SolidIndex (graph.h, sk = 1): a key's bucket = the top bits of min_remix(its minimizer),
 //                                first probe slot = sk_slot(key) -- as k_bucket_sk wrote them
 //
-// Record (uint4): x, y = bases 0..15, 16..31 (base i at bits 2i), z = bases 32..45 in bits
-// 0..27 | (n - 1) << 28; w = partition: bucket-bits-below-coarse (8) << 24 | p_rel (24 bits,
-// (read - g0) * M + first window).
-// Refined record (k_skrefine's output, what every bucket kernel reads): x, y and the low 28 bits
-// of z = the 2 (n + k - 1) base bits in CANONICAL orientation -- the smaller of the bases masked
-// to their length and their reverse complement, compared z, then y, then x, no flip on a tie --
-// with the bits past the record's length zero, so the words compare and hash as they are; the
-// top 4 bits of z stay n - 1; w = p | flip << 31, p = (read_base + read) * M + first window
+// Record (uint4): x, y, z = one 96-bit string, base i at bits 2i (x = bases 0..15, y = 16..31,
+// z = 32..46): the 2L base bits, ONE SET BIT at position 2L (the sentinel), zeros above it.
+// The length is the sentinel's position: L >= k >= 21 puts it in y or z, so 2L = 64 + the top
+// set bit of z, or 32 + that of y when z is 0 (sk2_len2: one clz and a select), and
+// n = L - k + 1.  47 bases take 94 bits, so a record holds up to 17 windows at k = 31 (a whole
+// run of the W = 17 block; 16 at k = 32).  w = partition: bucket-bits-below-coarse (8) << 24 |
+// p_rel (24 bits, (read - g0) * M + first window).
+// Refined record (k_skrefine's output, what every bucket kernel reads): the same string with
+// the bases in CANONICAL orientation -- the smaller of the L bases and their reverse complement,
+// compared z, then y, then x (without the sentinel), no flip on a tie -- so the words compare
+// and hash as they are; w = p | flip << 31, p = (read_base + read) * M + first window
 // (p < 2^31: phase_count_sk2 declines unless (read_base + reads) * 2M < 2^32).
 // Events as count_part.h: read = p / M, lf = p % M + o for window o, lr = 2M - 1 - lf; the
 // canonical record's windows by sk2_events (EA + o, EB - o).
@@ -40,7 +43,7 @@
 
 namespace ec {
 
-constexpr int SK2_NMAX = 16;     // windows per record (n - 1 in 4 bits)
+constexpr int SK2_NMAX = 17;     // windows per record (the W = 17 block of k = 31; 47 bases)
 // entries a partition wave buffers: 1024 (40 KB of LDS a workgroup at NPF = 7: four workgroups,
 // four waves a SIMD, per CU).  A round adds ~2 W / (W + 1) entries a lane (~114 a wave at
 // k = 31), at most 64 W: the buffer is flushed past SK2_FLUSH_AT, which leaves room for 10 entries
@@ -54,7 +57,7 @@ constexpr int SK2_FLUSH_AT = SK2_ECAP_W - 64 - 640;
 #endif
 constexpr int SK2_PD = SK2_PD_DEF;  // k_skbucket record rounds in flight per thread
 constexpr int SK2_HQ = 128;      // sampled runs a partition wave queues for the HyperLogLog
-constexpr int SK2_BASES = 46;    // bases per record (92 bits)
+constexpr int SK2_BASES = 47;    // bases per record (94 bits, the sentinel at bit 94 at most)
 #ifndef SK2_TILE_DEF
 #define SK2_TILE_DEF 2048
 #endif
@@ -63,8 +66,24 @@ constexpr int SK2_CBITS = 6;     // coarse buckets of the partition: 64
 constexpr int SK2_BBITS = 14;    // final buckets <= 2^14 (bucket bits in an entry)
 constexpr int SK2_FBITS = SK2_BBITS - SK2_CBITS;  // bucket bits below the coarse bits in a record
 
-__host__ __device__ constexpr inline uint32_t sk2_nmax(int k) {
-    return (uint32_t)(SK2_BASES - k + 1 < SK2_NMAX ? SK2_BASES - k + 1 : SK2_NMAX);
+// Partition entry (u32): lane (6) | first window (FW) | n - 1 (12 - FW) | top SK2_BBITS of
+// min_remix (14).  FW = 8 takes every M <= 256 with n <= 16; FW = 7 (M <= 128: reads up to
+// 158 bases at k = 31) gives n - 1 the fifth bit a 17-window run needs.  Only k = 31 has such
+// runs (k = 32: 47 bases hold 16 windows; k <= 30: the 4-bit field caps a run of equal hashes
+// at 16, which W <= 16 reaches only when an m-mer repeats inside the run).
+constexpr uint32_t SK2_FW17_MAXM = 128;
+__host__ __device__ constexpr inline uint32_t sk2_nmax(int k, int fw = 8) {
+    const int nb = SK2_BASES - k + 1, nf = 1 << (12 - fw);
+    return (uint32_t)(nb < nf ? (nb < SK2_NMAX ? nb : SK2_NMAX) : (nf < SK2_NMAX ? nf : SK2_NMAX));
+}
+// 2L of a record: the sentinel's position in the 96-bit string (it lies in y or z)
+__device__ inline unsigned int sk2_len2(uint32_t y, uint32_t z) {
+    return (z ? 95u : 63u) - (unsigned int)__clz((int)(z ? z : y));
+}
+__device__ inline unsigned int sk2_n(uint32_t y, uint32_t z, int k) { return sk2_len2(y, z) / 2 - (unsigned int)k + 1; }
+// window-count bin of a record, most windows first: SK2_NMAX - n in [0, SK2_NMAX) (clamped: an index)
+__device__ inline unsigned int sk2_bin(uint32_t y, uint32_t z, int k) {
+    return (unsigned int)SK2_NMAX - min(max(sk2_n(y, z, k), 1u), (unsigned int)SK2_NMAX);
 }
 
 // ---- partition -------------------------------------------------------------------------------
@@ -88,7 +107,7 @@ __device__ inline void sk_hll_put(unsigned int *s_hll, uint32_t hh) {
     }
 }
 
-template <int C>
+template <int C, int FW>
 __device__ inline void skpart_flush(uint32_t cntw, const uint32_t *ent, uint16_t *srt, unsigned int *wcnt,
                                     unsigned int *cur, unsigned long long *base, const uint32_t *rel,
                                     const uint32_t *st, uint32_t lane, unsigned long long gcap, uint64_t cap,
@@ -144,12 +163,15 @@ __device__ inline void skpart_flush(uint32_t cntw, const uint32_t *ent, uint16_t
         uint32_t qv = 0;
         if (i < cntw) {
             const uint32_t e = ent[srt[i]];
-            const uint32_t lr = e & 63u, w0 = (e >> 6) & 0xFFu, n1 = (e >> 14) & 15u;
+            const uint32_t lr = e & 63u, w0 = (e >> 6) & ((1u << FW) - 1u), n1 = (e >> (6 + FW)) & ((1u << (12 - FW)) - 1u);
             const uint32_t p0 = rel[lr] + w0;
+            // the run's L = n1 + k bases, the sentinel at bit 2L - 32 of (y, z), zeros above
+            const uint32_t sp = 2 * (n1 + (uint32_t)k) - 32, sbit = 1u << (sp & 31);
+            const uint32_t b1 = sk_bases16(st, p0 + 16), b2 = sk_bases16(st, p0 + 32);
             uint4 o;
             o.x = sk_bases16(st, p0);
-            o.y = sk_bases16(st, p0 + 16);
-            o.z = (sk_bases16(st, p0 + 32) & 0x0FFFFFFFu) | n1 << 28;
+            o.y = sp >= 32 ? b1 : (b1 & (sbit - 1u)) | sbit;
+            o.z = sp >= 32 ? (b2 & (sbit - 1u)) | sbit : 0u;
             o.w = ((e >> 18) & ((1u << SK2_FBITS) - 1)) << 24 | ((rtile + lr) * M + w0);
             recs[base[e >> 26] + i] = o;
             samp = ((e >> 18) & smaskb) == 0;
@@ -168,7 +190,8 @@ __device__ inline void skpart_flush(uint32_t cntw, const uint32_t *ent, uint16_t
 // Region of (c, g): records [(g * C + c) * cap, + cap) of recs, spill records at C * G * cap
 // (SK2_ECAP_W of them: a flush stores at most that many; *overflow set, the call is redone); cnt[c * G + g] = records stored.
 // elim (<= SK2_ECAP_W): the entries a wave may buffer (smaller only to test the overflow path).
-// Entry (u32): lane | first window << 6 | (n - 1) << 14 | top SK2_BBITS of min_remix << 18.
+// Entry (u32): lane | first window << 6 | (n - 1) << (6 + FW) | top SK2_BBITS of min_remix << 18
+// (sk2_nmax above: FW = 7 and nmax = 17 for N17, W = 17 and M <= SK2_FW17_MAXM; else FW = 8).
 // k_skpart_w: the partition for one compile-time window width W = k - m + 1 (the headline's k = 31: W = 17):
 // a round is one block of W m-mers, their hashes and the previous block's suffix minima held
 // in registers (van Herk / Gil-Werman: window rW + j = min(suffix_r[j], prefix_{r+1}[j - 1])),
@@ -179,7 +202,7 @@ __device__ inline void skpart_flush(uint32_t cntw, const uint32_t *ent, uint16_t
 // byte of a read is A, C, G or T (decode(encode(byte)) == byte: one v_perm per 4 bytes), no
 // tile outgrows the stage -- raises *vfail otherwise (the host then takes the prescan path),
 // and adds the windows to *npos.
-template <int NPF, int W, bool VAL>
+template <int NPF, int W, bool VAL, bool N17 = false>
 __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restrict__ buf,
                                                          const uint64_t *__restrict__ off, uint64_t nreads, MinCfg mc,
                                                          uint32_t M, uint64_t gsize, uint32_t G, uint64_t cap,
@@ -210,7 +233,10 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
     const uint64_t g0 = min(g * gsize, nreads), g1 = min(g0 + gsize, nreads);
     const uint32_t ntile = (uint32_t)((g1 - g0 + 63) / 64);
     const int k = mc.k;
-    constexpr uint32_t nmax = sk2_nmax(W + SK_M - 1);  // k = W + m - 1
+    static_assert(!N17 || W == 17, "17-window runs exist at k = 31 only");
+    constexpr int FW = N17 ? 7 : 8;                        // first-window bits of an entry (M <= 1 << FW)
+    constexpr int RST = (1 << 6) - (1 << (6 + FW));        // an entry's run-start term per window
+    constexpr uint32_t nmax = sk2_nmax(W + SK_M - 1, FW);  // k = W + m - 1
     const uint64_t kmask = kmask64(k);
     uint4 pf[NPF];
     uint64_t nx_base = 0;
@@ -297,17 +323,17 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
         const uint32_t nrounds = __any(has) ? (M + W - 1) / W : 0u;
         // the open run of a lane: windows [rs, w) of minimizer runv.  runv starts as window 0's
         // value, so window 0 never closes a run; a lane without a read never closes one (has).
-        // The run start is kept as its entry term rsx = -16320 rs (below): the close test
+        // The run start is kept as its entry term rsx = RST rs (below; -16320 rs at FW = 8): the close test
         // rs == end - nmax compares it with a uniform constant and the entry needs no multiply
         uint32_t runv = S[0], rsx = 0, cntw = 0;  // cntw: the wave's buffered entries (uniform)
         const uint64_t hasm = __builtin_amdgcn_ballot_w64(has);
         const uint32_t rtile = 64 * t;            // the tile's first read relative to g0
-        // entry of the run [rs, end) closing at window end: lane | rs << 6 | (n - 1) << 14 |
-        // bucket bits << 18 with n = end - rs (fields disjoint, so a sum: (end - 1) << 14 -
-        // 16320 rs), the bucket bits the top 14 of min_remix(runv) = its low 14 (the shift drops
+        // entry of the run [rs, end) closing at window end: lane | rs << 6 | (n - 1) << (6 + FW) |
+        // bucket bits << 18 with n = end - rs (fields disjoint, so a sum: (end - 1) << (6 + FW) +
+        // RST rs), the bucket bits the top 14 of min_remix(runv) = its low 14 (the shift drops
         // the rest)
-        auto entry = [&](uint32_t end) { return (runv << 18) + lane + (((end - 1u) << 14) + rsx); };
-        auto rs_term = [](uint32_t w) { return (uint32_t)((int)w * -16320); };
+        auto entry = [&](uint32_t end) { return (runv << 18) + lane + (((end - 1u) << (6 + FW)) + rsx); };
+        auto rs_term = [](uint32_t w) { return (uint32_t)((int)w * RST); };
         for (uint32_t round = 0; round < nrounds; round++) {
             const uint32_t w0 = round * W;  // first window of the round
             // m-mer (round + 1) W + j covers bases q + j .. q + j + m - 1: a0, a1 = bases q .. q + 31
@@ -335,14 +361,14 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
                 const uint32_t end = w0 + j;  // uniform
                 // (the mask from the compares' own ballots: a ballot of the combined bool was
                 // materialised through a VGPR)
-                const bool c1 = v != runv, c2 = rsx == rw0 + (uint32_t)((j - (int)nmax) * -16320);
+                const bool c1 = v != runv, c2 = rsx == rw0 + (uint32_t)((j - (int)nmax) * RST);
                 const bool close = has & (c1 | c2);
                 const uint64_t bal = (__builtin_amdgcn_ballot_w64(c1) | __builtin_amdgcn_ballot_w64(c2)) & hasm;
                 if (close) {
                     const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
                     ent[min(cntw, elim - 64) + rk] = entry(end);  // (a uniform clamp: in bounds; past it, *overflow)
-                    rsx = rw0 + (uint32_t)(j * -16320);
+                    rsx = rw0 + (uint32_t)(j * RST);
                 }
                 cntw += (uint32_t)__popcll(bal);
                 runv = v;
@@ -368,7 +394,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
             }
             // flush: the buffer may not take another round
             if (round + 1 < nrounds && cntw > elim - 64 - 640) {
-                skpart_flush<C>(cntw, ent, s_srt[wid], s_wcnt[wid], s_cur, s_base[wid], s_rel[wid], st, lane, gcap,
+                skpart_flush<C, FW>(cntw, ent, s_srt[wid], s_wcnt[wid], s_cur, s_base[wid], s_rel[wid], st, lane, gcap,
                                 cap, spill, M, rtile, recs, overflow, s_hll, s_hq[wid], smask ? 0xFFu : 0u, k,
                                 kmask);
                 cntw = 0;
@@ -386,7 +412,7 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
                 ent[cntw + rk] = entry(M);  // (cntw <= elim - 64 here)
             }
             cntw += (uint32_t)__popcll(bal);
-            skpart_flush<C>(cntw, ent, s_srt[wid], s_wcnt[wid], s_cur, s_base[wid], s_rel[wid], st, lane, gcap,
+            skpart_flush<C, FW>(cntw, ent, s_srt[wid], s_wcnt[wid], s_cur, s_base[wid], s_rel[wid], st, lane, gcap,
                             cap, spill, M, rtile, recs, overflow, s_hll, s_hq[wid], smask ? 0xFFu : 0u, k, kmask);
         }
     }
@@ -413,17 +439,18 @@ __device__ inline uint32_t rev2_32b(uint32_t v) {  // superkmer.h rev2_32 with o
     v = __builtin_bitreverse32(v);
     return ((v >> 1) & 0x55555555u) | ((v & 0x55555555u) << 1);
 }
-// Canonical content of a partition record, in place: its L = n + k - 1 bases masked to L (the
-// partition copies bases past the run too) or their reverse complement, whichever is smaller
-// (compared z, then y, then x; no flip on a tie); z keeps (n - 1) << 28.  Returns the flip.
+// Canonical content of a partition record, in place: its L bases (the sentinel taken off) or
+// their reverse complement, whichever is smaller (compared z, then y, then x; no flip on a
+// tie), the sentinel put back at bit 2L.  Returns the flip.
 // Branch-free: selects, no divergent paths.
-__device__ inline bool sk2_canon(uint32_t &r0, uint32_t &r1, uint32_t &r2, int k) {
-    const unsigned int n = (r2 >> 28) + 1, L2 = 2 * (n + (unsigned int)k - 1);  // 2L in [2k, 92]
-    const uint32_t m1 = L2 >= 64 ? 0xFFFFFFFFu : (1u << ((L2 - 32) & 31)) - 1u;  // bits of word 1
-    const uint32_t mw2 = L2 > 64 ? (1u << ((L2 - 64) & 31)) - 1u : 0u;           // bits of word 2
+__device__ inline bool sk2_canon(uint32_t &r0, uint32_t &r1, uint32_t &r2) {
+    const unsigned int L2 = sk2_len2(r1, r2);  // 2L in [42, 94]
+    const uint32_t sbit = 1u << (L2 & 31);     // the sentinel in its word
+    const uint32_t m1 = L2 >= 64 ? 0xFFFFFFFFu : sbit - 1u;  // bits of word 1
+    const uint32_t mw2 = L2 >= 64 ? sbit - 1u : 0u;          // bits of word 2
     const uint32_t x0 = r0, x1 = r1 & m1, x2 = r2 & mw2;
     // reverse complement of the L bases: rev2 of the 96-bit string (base i -> 47 - i), then
-    // down by 96 - 2L bits (4 .. 54), complemented
+    // down by 96 - 2L bits (2 .. 54), complemented
     const uint32_t y0 = rev2_32b(x2), y1 = rev2_32b(x1), y2 = rev2_32b(x0);
     const unsigned int sft = 96 - L2, s5 = sft & 31;
     const bool lo = sft < 32;
@@ -431,7 +458,9 @@ __device__ inline bool sk2_canon(uint32_t &r0, uint32_t &r1, uint32_t &r2, int k
                    a2 = y2 >> s5;
     const uint32_t q0 = ~(lo ? a0 : a1), q1 = ~(lo ? a1 : a2) & m1, q2 = lo ? ~a2 & mw2 : 0u;
     const bool flip = q2 != x2 ? q2 < x2 : q1 != x1 ? q1 < x1 : q0 < x0;
-    r0 = flip ? q0 : x0, r1 = flip ? q1 : x1, r2 = (flip ? q2 : x2) | (n - 1) << 28;
+    r0 = flip ? q0 : x0;
+    r1 = (flip ? q1 : x1) | (L2 >= 64 ? 0u : sbit);
+    r2 = (flip ? q2 : x2) | (L2 >= 64 ? sbit : 0u);
     return flip;
 }
 // Events of a refined record (w = p | flip << 31, n windows): with rd = p / M, rm = p % M,
@@ -525,7 +554,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_skrefine(const uint4 *recs, 
 #ifdef SK2_CHECK_P31  // debug builds (make EXTRA=-DSK2_CHECK_P31): the kernel aborts on a position past 2^31
                 assert((p >> 31) == 0);
 #endif
-                rw[q] = p | (uint32_t)sk2_canon(rx[q], ry[q], rz[q], k) << 31;
+                rw[q] = p | (uint32_t)sk2_canon(rx[q], ry[q], rz[q]) << 31;
             }
         }
         __syncthreads();
@@ -600,8 +629,8 @@ struct EvExpand {  // e -> (read << 32) | l for the dense arrays
 // At ~150-fold coverage a bucket's records are mostly the same few super-k-mers read again and
 // again (each interior super-k-mer of the genome appears in ~130 reads, in two orientations).  The
 // records first go through an LDS table keyed by their CANONICAL content -- the L = n + k - 1
-// bases masked to L (the partition copies bases past the run too) or their reverse complement,
-// whichever is smaller, plus n -- keeping per distinct record its multiplicity and two event
+// bases or their reverse complement, whichever is smaller, with the length's sentinel bit --
+// keeping per distinct record its multiplicity and two event
 // minima: with A = read 2M + first window and B = read 2M + 2M - 1 - first window, window o's
 // k-mer string was inserted by build() at A + o and its twin at B - o (count_part.h events); a
 // record taken in reverse complement has A' = B - n + 1, B' = A + n - 1 (window o' of the flip is
@@ -667,7 +696,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_skbucket(const uint4 *recs, 
     // the n windows of a (canonical) record into the k-mer table: window o's string was inserted
     // at ea + o, its twin at eb - o, mult times each
     auto roll_out = [&](uint32_t x0, uint32_t x1, uint32_t x2, unsigned int mult, unsigned int ea, unsigned int eb) {
-        const unsigned int n = (x2 >> 28) + 1;
+        const unsigned int n = min(sk2_n(x1, x2, k), (unsigned int)SK2_NMAX);  // (the bound: a loop count)
         if (dbg) n_rolled += n;
         auto events = [&](uint64_t fwd, uint64_t rc, unsigned int o, unsigned int &eC, unsigned int &eT,
                           unsigned int &add) {
@@ -763,7 +792,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_skbucket(const uint4 *recs, 
             // used), so the loads stay in order in flight and the wait before use is vmcnt(PD - 1)
             nxd[j] = recs[min(ri + PD * ROUND, r1 - 1)];
             // canonical content and flip as the refine left them; events of window 0
-            const unsigned int n = (x.z >> 28) + 1;
+            const unsigned int n = sk2_n(x.y, x.z, k);
             K0[j] = x.x, K1[j] = x.y, K2[j] = x.z;
             sk2_events(x.w, n, M, inv_m, EA[j], EB[j]);
             // content hash -> first slot, tag
@@ -870,7 +899,7 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_skbucket(const uint4 *recs, 
             const unsigned int i = tid + q * BUCKET_THREADS;
             sl[q] = SK2_NMAX;
             if (i < (unsigned)RS && r_tag[i]) {
-                sl[q] = SK2_NMAX - 1 - (r_z[i] >> 28);
+                sl[q] = sk2_bin(r_y[i], r_z[i], k);
                 rk[q] = atomicAdd(&s_ncnt[sl[q]], 1u);
             }
         }
@@ -922,7 +951,10 @@ __global__ void __launch_bounds__(BUCKET_THREADS) k_skbucket(const uint4 *recs, 
 // list raises *overflow (the call is redone on another path).
 template <int SLOTS, int RS, int NT>
 struct SkB3Lds {
-    static constexpr int NC = RS / 2;  // compact records (CLAIM_MAX <= RS / 2)
+    // compact records: as many as the record table's space holds beside the k-mer table (1088 of
+    // RS = 1664 -- a whole 17-window run is one more distinct record where short reads also
+    // bring each of its prefixes and suffixes, which the 16 + 1 pieces coincided with)
+    static constexpr int NC = (int)((7 * RS * sizeof(uint32_t) - sizeof(LTabE<SLOTS>)) / (6 * sizeof(uint32_t)));
     struct Rec {
         uint32_t tag[RS], x[RS], y[RS], z[RS], mult[RS], a[RS], b[RS];
     };
@@ -948,7 +980,8 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
                                                   unsigned int claim_cap, unsigned int *bmark = nullptr) {
     constexpr int SBITS = __builtin_ctz(SLOTS);
     constexpr uint32_t PEND = 0x800u;
-    constexpr unsigned int CLAIM_MAX = RS / 2 < RS - 1 - NT ? RS / 2 : RS - 1 - NT;
+    constexpr int NCR = SkB3Lds<SLOTS, RS, NT>::NC;  // entries the compact arrays take
+    constexpr unsigned int CLAIM_MAX = NCR < RS - 1 - NT ? NCR : RS - 1 - NT;
     static_assert(RS > NT + 1, "record table too small for the records in flight");
     static_assert(sizeof(typename SkB3Lds<SLOTS, RS, NT>::Roll) <= sizeof(typename SkB3Lds<SLOTS, RS, NT>::Rec),
                   "the k-mer table and the compact records fit the record table's space");
@@ -975,7 +1008,7 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
 
     // the n windows of a canonical record into the k-mer table (as k_skbucket's roll_out)
     auto roll_out = [&](uint32_t x0, uint32_t x1, uint32_t x2, unsigned int mult, unsigned int ea, unsigned int eb) {
-        const unsigned int n = (x2 >> 28) + 1;
+        const unsigned int n = min(sk2_n(x1, x2, k), (unsigned int)SK2_NMAX);  // (the bound: a loop count)
         if (dbg) n_rolled += n;
         auto events = [&](uint64_t fwd, uint64_t rc, unsigned int o, unsigned int &eC, unsigned int &eT,
                           unsigned int &add) {
@@ -1051,7 +1084,7 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
         const bool valid = ri < r1;
         const uint4 x = nxd;
         nxd = recs[min(ri + PD * NT, r1 - 1)];
-        const unsigned int n = (x.z >> 28) + 1;
+        const unsigned int n = sk2_n(x.y, x.z, k);
         const uint32_t K0 = x.x, K1 = x.y, K2 = x.z;  // canonical as the refine left them
         uint32_t EA, EB;
         sk2_events(x.w, n, M, inv_m, EA, EB);
@@ -1076,7 +1109,7 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
             if (go && !hit && T != 0 && T != (TG | PEND)) SL = SL + 1 == (unsigned int)RS ? 0u : SL + 1;
             if (claim) {
                 // reserve an entry first, so the table never holds more than the cap (the compact
-                // arrays below hold NC = RS / 2 entries): a lane past it, or one whose CAS loses,
+                // arrays below hold NC entries): a lane past it, or one whose CAS loses,
                 // gives its reservation back (claim_cap: tests of the overflow list)
                 const unsigned int o = atomicAdd(&s_nent, 1u);
                 if (o >= min(CLAIM_MAX, claim_cap)) {
@@ -1129,7 +1162,7 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
         bin[q] = SK2_NMAX;
         if (i < (unsigned)RS && R.tag[i]) {
             cx[q] = R.x[i], cy[q] = R.y[i], cz[q] = R.z[i], cm[q] = R.mult[i], ca[q] = R.a[i], cb[q] = R.b[i];
-            bin[q] = SK2_NMAX - 1 - (cz[q] >> 28);  // most windows first
+            bin[q] = sk2_bin(cy[q], cz[q], k);  // most windows first
             rk[q] = atomicAdd(&s_ncnt[bin[q]], 1u);
         }
     }
@@ -1201,8 +1234,8 @@ __global__ void __launch_bounds__(NT) k_skbucket3(const uint4 *recs, const unsig
 // p^2, p = 1 - exp(-2D/m) = 0.14: ~170 singletons a table; 2^16 cells passed ~600 and overflowed
 // the 1474-key budget in many buckets
 constexpr int SKF_BITS = 17;  // filter cells per bitmap
-// MERGED (round 5): the bucket's records merged by k_skdedup first -- {canonical bases | (n - 1)
-// << 28, multiplicity} with their event minima {A, B} in mev -- so a super-k-mer read ~130 times
+// MERGED (round 5): the bucket's records merged by k_skdedup first -- {canonical bases and
+// sentinel, multiplicity} with their event minima {A, B} in mev -- so a super-k-mer read ~130 times
 // rolls out its windows once, with add = multiplicity (a key of a record seen twice is repeated:
 // its cells are marked seen twice at once, and it is inserted without the filter's test)
 template <int SLOTS, int NT, bool EVEN_K, bool MERGED = false>
@@ -1232,10 +1265,10 @@ __global__ void __launch_bounds__(NT) k_skbucket_filt(const uint4 *recs, const u
     const uint64_t r0 = bbeg[b], r1 = bend[b];
     const uint64_t kmask = kmask64(k);
     const int fsh = 64 - 2 * k;
-    // the windows of a record (window o = bases o .. o + k - 1, o < n <= 16): canonical key, add,
+    // the windows of a record (window o = bases o .. o + k - 1, o < n <= 17): canonical key, add,
     // first events of the canonical / twin string (k_skbucket3's roll-out)
     auto windows = [&](uint64_t ri, const uint4 &x, auto &&fn) {
-        const unsigned int n = (x.z >> 28) + 1;
+        const unsigned int n = min(sk2_n(x.y, x.z, k), (unsigned int)SK2_NMAX);  // (the bound: a loop count)
         // window o of the canonical bases was inserted at EA + o, its twin at EB - o, mult times:
         // a merged record brings its event minima and multiplicity, a refined one its position
         uint32_t EA, EB;
@@ -1247,7 +1280,9 @@ __global__ void __launch_bounds__(NT) k_skbucket_filt(const uint4 *recs, const u
             sk2_events(x.w, n, M, inv_m, EA, EB);
         }
         for (unsigned int o = 0; o < n; o++) {
-            const uint32_t lo = __builtin_amdgcn_alignbit(x.y, x.x, 2 * o), hi = __builtin_amdgcn_alignbit(x.z, x.y, 2 * o);
+            // (alignbit shifts by 2o mod 32: window 16, the 17th, starts at word y)
+            const uint32_t lo = o < 16 ? __builtin_amdgcn_alignbit(x.y, x.x, 2 * o) : x.y,
+                           hi = o < 16 ? __builtin_amdgcn_alignbit(x.z, x.y, 2 * o) : x.z;
             const uint64_t P = (uint64_t)lo | (uint64_t)hi << 32;
             const uint64_t rv = ~P & kmask, fw = rev2_64(P) >> fsh;
             const bool tw = fw > rv;
@@ -1349,7 +1384,7 @@ __global__ void __launch_bounds__(NT) k_skbucket_filt(const uint4 *recs, const u
 // At 0.5 % substitutions ~60 % of the reads are error-free and most super-k-mers of the others
 // are too: ecoli10m_err's buckets hold ~6300 records of which ~1200 are distinct.  k_skdedup merges
 // a bucket's records by canonical content (k_skbucket3's record table and claim protocol) and
-// writes the distinct ones -- {bases | (n - 1) << 28, multiplicity} + {A, B} -- at the bucket's
+// writes the distinct ones -- {bases and sentinel, multiplicity} + {A, B} -- at the bucket's
 // start in mrec / mev; a record past the table's claim cap is written as it is (multiplicity 1,
 // any split of the copies between entries is exact).  k_skbucket_filt<MERGED> then rolls out
 // ~6x fewer windows, twice.  mend[b] = the end of bucket b's merged records.  (Round 4 merged in
@@ -1383,7 +1418,7 @@ __global__ void __launch_bounds__(NT) k_skdedup(const uint4 *recs, const unsigne
         const bool valid = ri < r1;
         const uint4 x = nxt;
         if (c0 + NT < r1) nxt = recs[min(ri + NT, r1 - 1)];
-        const unsigned int n = (x.z >> 28) + 1;
+        const unsigned int n = sk2_n(x.y, x.z, k);
         const uint32_t K0 = x.x, K1 = x.y, K2 = x.z;  // canonical as the refine left them
         uint32_t EA, EB;
         sk2_events(x.w, n, M, inv_m, EA, EB);
@@ -1441,7 +1476,7 @@ __global__ void __launch_bounds__(NT) k_skdedup(const uint4 *recs, const unsigne
         const unsigned int i = tid + q * NT;
         bin[q] = SK2_NMAX;
         if (i < (unsigned int)RS && tag[i]) {
-            bin[q] = SK2_NMAX - 1 - (tz[i] >> 28);
+            bin[q] = sk2_bin(ty[i], tz[i], k);
             rk[q] = atomicAdd(&s_ncnt[bin[q]], 1u);
         }
     }
