@@ -3,7 +3,7 @@
 // The reference's GPU path starts from reads in host memory (src/eulercuda.py:484-497: the
 // read buffer goes to encode_lmer_device and is copied H2D there).  Here the host reads reach
 // HBM in chunks on a copy stream while the session stream already partitions the chunks that
-// have arrived (assemble.hip pipe_upto).  Reads come as ASCII (ec_assemble_host) or 2 bits per
+// have arrived (session.h pipe_upto).  Reads come as ASCII (ec_assemble_host) or 2 bits per
 // base (ec_assemble_packed_host, a quarter of the PCIe bytes): k_unpack2 expands a chunk of
 // codes to the ASCII layout every count kernel reads, k_patch restores the bytes that are not
 // A/C/G/T (N and anything else: the count path then treats them as it treats ASCII input).

@@ -1,16 +1,25 @@
 // session.h -- the host side of a session: its device / pinned buffers, ec_session itself, the
-// resets of its device-backed state and the small device -> host reads.  Included by assemble.hip
-// after the kernel headers whose types the session holds (SolidIndex, XAlpha, SuperRec).
+// resets of its device-backed state and the small device -> host reads; then what the count phases
+// (count_phase.h) and the graph phase (assemble.hip) both stand on: the device scalars block, the
+// rocprim scan / sort wrappers, the host-input pipeline's pipe_upto, the timing marks,
+// compact_table and the shared checks.  Included by assemble.hip after the kernel headers whose
+// types the session holds (SolidIndex, XAlpha, SuperRec).
 //
 // A device buffer of a session exists only through EC_SESSION_BUFS below: the list expands to the
 // DevBuf members and to for_each_buf, so what ec_session_bytes counts, ec_session_trim releases
 // and the destructor frees is by construction every buffer there is.
 #pragma once
 #include "common.h"
+#include "compact.h"
+#include "graph.h"
+#include "hostin.h"
+
+#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <dlfcn.h>
@@ -455,5 +464,144 @@ inline int host_sync(ec_session *s, hipStream_t st) {
         return EC_ERR_HIP;
     }
     return EC_OK;
+}
+
+struct Scalars {  // device scalars block
+    unsigned long long npos;
+    unsigned long long bad;
+    unsigned long long ndistinct;
+    double est;
+    unsigned int overflow;
+    unsigned int nsolid;
+    unsigned int nstarts;
+    unsigned int final_sel;
+    unsigned int ndict;
+    unsigned int nr;
+    unsigned int npal;
+    unsigned int ngath;  // phase_load_det: non-filler records of a gathered solid set
+    unsigned long long nvisited;
+    unsigned int maxlocal;
+    unsigned int skew;
+    unsigned int lens[4];  // k_upsweep: max read length, ~min read length (reads with windows), any slow-path read
+    unsigned long long nrec;  // k_upsweep_sk: super-k-mer records
+    unsigned int nasym, nxl, nxs;  // extended.h: one-way links, entries of their components, their starts
+    unsigned int xbad;             // extended.h: a walk that never reaches its start again
+    unsigned int wbv_long, wpad;     // k_wbv: a read of another length
+    unsigned long long chains;       // k_tile_compact: the tile contraction's chain count
+    unsigned int active[64];
+};
+static_assert(sizeof(Scalars) % 8 == 0 && offsetof(Scalars, bad) % 8 == 0, "k_scal_reset writes 64-bit words");
+
+// the scalars as a call finds them, in one launch (two fills before): all zero, bad = ~0
+__global__ void __launch_bounds__(64) k_scal_reset(Scalars *sc) {
+    unsigned long long *w = reinterpret_cast<unsigned long long *>(sc);
+    for (unsigned int i = threadIdx.x; i < sizeof(Scalars) / 8; i += 64)
+        w[i] = i == offsetof(Scalars, bad) / 8 ? ~0ull : 0ull;
+}
+
+int scan_u64(ec_session *s, const unsigned long long *in, unsigned long long *out, size_t n) {
+    size_t bytes = 0;
+    EC_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0ull, n, rocprim::plus<unsigned long long>(), s->stream));
+    EC_CHECK(s->tmp.ensure(bytes));
+    EC_HIP(rocprim::exclusive_scan(s->tmp.p, bytes, in, out, 0ull, n, rocprim::plus<unsigned long long>(), s->stream));
+    return EC_OK;
+}
+
+int scan_excl_u32(ec_session *s, const unsigned int *in, unsigned int *out, size_t n) {
+    size_t bytes = 0;
+    EC_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, rocprim::plus<unsigned int>(), s->stream));
+    EC_CHECK(s->tmp.ensure(bytes));
+    EC_HIP(rocprim::exclusive_scan(s->tmp.p, bytes, in, out, 0u, n, rocprim::plus<unsigned int>(), s->stream));
+    return EC_OK;
+}
+
+int scan_incl_u32(ec_session *s, const unsigned int *in, unsigned int *out, size_t n) {
+    size_t bytes = 0;
+    EC_HIP(rocprim::inclusive_scan(nullptr, bytes, in, out, n, rocprim::plus<unsigned int>(), s->stream));
+    EC_CHECK(s->tmp.ensure(bytes));
+    EC_HIP(rocprim::inclusive_scan(s->tmp.p, bytes, in, out, n, rocprim::plus<unsigned int>(), s->stream));
+    return EC_OK;
+}
+
+int sort_pairs(ec_session *s, unsigned long long *kin, unsigned long long *kout, unsigned int *vin, unsigned int *vout,
+               size_t n) {
+    size_t bytes = 0;
+    EC_HIP(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, 0, 64, s->stream));
+    EC_CHECK(s->tmp.ensure(bytes));
+    EC_HIP(rocprim::radix_sort_pairs(s->tmp.p, bytes, kin, kout, vin, vout, n, 0, 64, s->stream));
+    return EC_OK;
+}
+
+// make host-input chunks .. c visible on the session stream (no-op without a pipeline)
+int pipe_upto(ec_session *s, int c) {
+    auto &pp = s->pipe;
+    if (!pp.active) return EC_OK;
+    c = std::min(c, pp.nchunks - 1);
+    if (pp.done > c) return EC_OK;
+    const int first = pp.done;
+    for (; pp.done <= c; pp.done++) EC_HIP(hipStreamWaitEvent(s->stream, pp.ev[pp.done], 0));
+    // one unpack over the chunks made visible together (their ranges are contiguous)
+    const uint64_t blo = pp.blo[first], bhi = pp.bhi[c], elo = pp.elo[first], ehi = pp.ehi[c];
+    if (pp.packed && bhi > blo) {
+        const uint64_t units = ((bhi + 15) >> 4) - (blo >> 4);
+        k_unpack2<<<grid_for(units, 256, 16384), 256, 0, s->stream>>>(pp.codes, blo, bhi, pp.ascii);
+        if (ehi > elo)
+            k_patch<<<grid_for(ehi - elo, 256, 4096), 256, 0, s->stream>>>(pp.exc_pos, pp.exc_byte, elo, ehi,
+                                                                           pp.ascii);
+    }
+    return EC_OK;
+}
+int pipe_all(ec_session *s) { return s->pipe.active ? pipe_upto(s, s->pipe.nchunks - 1) : EC_OK; }
+
+inline void mark(ec_session *s, int idx) {
+    if (s->stage_timing) {
+        hipEventRecord(s->ev[idx], s->stream);
+        if (idx & 1) s->sused[idx >> 1] = true;
+    }
+}
+// kernel-level timing events: kernel id, 0 = before / 1 = after
+inline void kmark(ec_session *s, int kid, int end) {
+    if (s->timing) {
+        hipEventRecord(s->kev[2 * kid + end], s->stream);
+        if (end) s->kused[kid] = true;
+    }
+}
+
+// solid slots of an HBM table -> dense arrays (ids in table order); sets dsc->nsolid / ndistinct
+template <typename SlotT, typename KeyT>
+int compact_table(ec_session *s, SlotT *table, uint64_t cap, long long limit, KeyT *dkey) {
+    hipStream_t st = s->stream;
+    Scalars *dsc = s->scal.as<Scalars>();
+    const unsigned int nblk = (unsigned int)((cap + COMPACT_CHUNK - 1) / COMPACT_CHUNK);
+    EC_CHECK(s->rbc.ensure((size_t)nblk * 8 + 8));
+    unsigned int *bc = s->rbc.as<unsigned int>(), *bs = bc + nblk;
+    EC_HIP(hipMemsetAsync(&dsc->nsolid, 0, 4, st));
+    EC_HIP(hipMemsetAsync(&dsc->ndistinct, 0, 8, st));
+    k_compact_count<SlotT><<<nblk, 256, 0, st>>>(table, cap, limit, bc, &dsc->ndistinct);
+    EC_CHECK(scan_incl_u32(s, bc, bs, nblk));
+    k_compact_write<SlotT, KeyT><<<nblk, 256, 0, st>>>(table, cap, limit, bs, dkey, s->dcnt.as<unsigned int>(),
+                                                      s->dfc.as<unsigned long long>(),
+                                                      s->dft.as<unsigned long long>());
+    k_compact_total<<<1, 1, 0, st>>>(bs, nblk, &dsc->nsolid);
+    return EC_OK;
+}
+
+
+// 2 U node ids (a solid k-mer and its twin) must leave bit 31 (CYC) free
+int check_node_ids(unsigned int U) {
+    if (2ull * U >= (unsigned long long)CYC) {
+        set_error("too many solid k-mers (%u) for 31-bit node ids", U);
+        return EC_ERR_CAPACITY;
+    }
+    return EC_OK;
+}
+
+// the prescan's first byte outside {A,C,G,T,N} (Scalars::bad, ~0 = none) as EC_ERR_ALPHABET
+int check_alphabet(const uint8_t *d_reads, unsigned long long bad) {
+    if (bad == ~0ull) return EC_OK;
+    uint8_t byte = 0;
+    hipMemcpy(&byte, d_reads + bad, 1, hipMemcpyDeviceToHost);
+    set_error("byte %llu (0x%02x) outside {A,C,G,T,N}", bad, byte);
+    return EC_ERR_ALPHABET;
 }
 }  // namespace

@@ -3,22 +3,25 @@ the count path the dispatch gives every cell.  Shared by test_kernel_grid.py (no
 reach every instantiation, every cell's reference result is non-trivial) and
 test_kernel_grid_gpu.py (every cell bit-exact against the oracle, on the predicted path).
 
-The dispatch, restated (csrc/assemble.hip unless another file is named; L = the one length of
-the reads that have windows, n = reads, M = L - k + 1 windows a read):
+The dispatch, restated (functions of csrc/count_phase.h unless another file is named; L = the one
+length of the reads that have windows, n = reads, M = L - k + 1 windows a read):
 
   k <= 32   phase_count_v2 stages 64-read wave tiles in NPF = 4 / 7 / 10 KiB a wave
-            (npf_of, :1098); with a stage (L <= 159)
-              21 <= k <= 32  k_skpart_w<NPF, k - 14, VAL> (:750-792): VAL = true without a
-                             prescan when the first read has windows (:1104-1116), VAL = false
-                             after the prescan when it is shorter than k (:1154)
-              otherwise      k_partition<NPF, k >= 17, R10> (:1199), R10 as EULERHIP_V2_R10
-                             forces it where k >= 16 (:1171)
-            without one (L >= 160, :1153) count_part.h's exact path (:1348-); and after
-            k_partition where the input has too few distinct keys for its fixed capacities
-            (:1216, :1290: k <= 4 here, see window_record_capacity_holds)
-  k >= 33   phase_count_w (:2264): k <= 52 and k <= L <= 160 k_wbv<k - 14> and minimizer runs
-            (:1937-1969), else hash buckets on the staged upsweep (count_wide.h k_upsweep_w)
-            while a 256-read tile fits STAGE_W bytes, else the HBM table (:2018, :2281-)
+            (its npf_of); with a stage (L <= 159)
+              21 <= k <= 32  k_skpart_w<NPF, k - 14, VAL> (skpart_kernel, launched by
+                             sk2_partition): VAL = true without a prescan when the first read has
+                             windows (phase_count_v2's fast path), VAL = false after the prescan
+                             when it is shorter than k (phase_count_v2, `if (allow_sk2)`)
+              otherwise      k_partition<NPF, k >= 17, R10> (phase_count_v2, EC_PARTITION), R10 as
+                             EULERHIP_V2_R10 forces it where k >= 16 (phase_count_v2, `r10`)
+            without one (L >= 160: phase_count_v2 returns at `!npf`) count_part.h's exact path
+            (phase_count); and after k_partition where the input has too few distinct keys for
+            its fixed capacities (phase_count_v2's overflow / skew returns: k <= 4 here, see
+            window_record_capacity_holds)
+  k >= 33   phase_count_w: k <= 52 and k <= L <= 160 k_wbv<k - 14> and minimizer runs
+            (phase_count_wpart, `mb`), else hash buckets on the staged upsweep (count_wide.h
+            k_upsweep_w) while a 256-read tile fits STAGE_W bytes, else the HBM table
+            (phase_count_wpart's `lens[2]` return, phase_count_w's table loop)
 """
 import numpy as np
 
@@ -41,7 +44,7 @@ TILE_READS = 256     # count_part.h
 
 
 def npf_of(L):
-    """staged KiB per wave of a 64-read tile of reads of <= L bases, 0: none (assemble.hip:1098;
+    """staged KiB per wave of a 64-read tile of reads of <= L bases, 0: none (phase_count_v2, npf_of;
     the 30: up to 15 bytes before the tile's first byte and after its last one, rounding the
     16-byte loads)"""
     need16 = (64 * L + 30 + 15) // 16
@@ -69,11 +72,13 @@ def window_record_capacity_holds(buf, off, k):
     one length: they are sized for keys that a hash spreads evenly (count_v2.h:4-8, :25), and an
     input with fewer distinct keys than that needs -- k = 1 has two canonical keys for 32 coarse
     buckets -- outgrows them, by design; the call is then redone on the exact path.
-      :1176, :1216  a (coarse bucket, 64-read group) run holds 5/4 of its even share + 128
-                    records (k_partition sets `overflow` past it, count_v2.h:351)
-      :1225, :1290  a final bucket holds 5/4 of its even share + 1024 records (k_refine2 sets
-                    `skew`); with <= 2 080 keys the estimate plans the 32 coarse buckets as the
-                    final ones (:1220)
+    Both in count_phase.h's phase_count_v2:
+      `cap`, and its return at `hsc.overflow`:  a (coarse bucket, 64-read group) run holds 5/4 of
+                    its even share + 128 records (k_partition sets `overflow` past it,
+                    count_v2.h:351)
+      `fcap`, and its return at `hsc.skew`:  a final bucket holds 5/4 of its even share + 1024
+                    records (k_refine2 sets `skew`); with <= 2 080 keys the estimate plans the 32
+                    coarse buckets as the final ones (its `bbits` loop)
     The bucket of a key is the top 5 bits of mix64(key) (count_v2.h:306-311)."""
     n = len(off) - 1
     L = int(off[1] - off[0])
@@ -88,7 +93,7 @@ def window_record_capacity_holds(buf, off, k):
         rc |= (np.uint64(3) - code[:, t:t + M]) << np.uint64(2 * t)
     with np.errstate(over="ignore"):
         bucket = (_mix64(np.minimum(fwd, rc)) >> np.uint64(59)).astype(np.int64)
-    group = (np.arange(n) // 64)[:, None]  # groups of one 64-read tile up to 2048 x 64 reads (:1093-1097)
+    group = (np.arange(n) // 64)[:, None]  # groups of one 64-read tile up to 2048 x 64 reads (phase_count_v2, G / gsize)
     runs = np.bincount((group * 32 + bucket).reshape(-1), minlength=32 * ((n + 63) // 64))
     cap = (64 * M * 5 // 4 + 31) // 32 + 128
     fcap = n * M * 5 // 4 // 32 + 1024
@@ -100,33 +105,37 @@ def expected_path(k, L, n, no_sk2=False, r10=-1, reads=None):
     (reads shorter than k beside them change nothing below: the prescan takes the lengths of the
     reads with windows, count_v2.h:81-87).  no_sk2: EULERHIP_NO_SK2; r10: EULERHIP_V2_R10;
     reads: the (buf, offsets) counted where they are not reads_of(k, L, n) (looked at for
-    k <= FEW_KEYS_K only).  Every rule cites its line of csrc/assemble.hip."""
+    k <= FEW_KEYS_K only).  Every rule cites its function of csrc/count_phase.h (assemble.hip
+    where named)."""
     assert 1 <= k <= 63 and L >= k and n >= 1
-    if k <= 32:  # :4037
-        v2 = npf_of(L) != 0  # :1153: a wave stage holds the tile
+    if k <= 32:  # assemble.hip, assemble: phase_count for k <= 32
+        v2 = npf_of(L) != 0  # phase_count_v2, `if (!npf)`: a wave stage holds the tile
         if v2 and k <= FEW_KEYS_K:  # too few distinct keys for the fixed capacities: see there
             v2 = window_record_capacity_holds(*(reads or reads_of(k, L, n)), k)
         if v2:
-            # :707, :717: super-k-mer records (M <= 256, a group's windows < 2^24 and 2 n M < 2^32
-            # hold for every input of this size; the estimate of so few keys plans no filter, :863)
+            # sk2_shape: super-k-mer records (M <= 256, a group's windows < 2^24 and 2 n M < 2^32
+            # hold for every input of this size; the estimate of so few keys plans no filter, sk2_plan)
             if SK_MIN_K <= k <= 32 and not no_sk2:
-                return EC_PATH_PARTITIONED, 3, 16  # :1060-1063
+                return EC_PATH_PARTITIONED, 3, 16  # phase_count_sk2, its stats at `done = true`
             # (k > FEW_KEYS_K: >= 8 192 canonical keys and ~3 000 distinct ones in the input, ~94 a
-            # coarse bucket: no run or bucket comes near 5/4 of its even share, :1176, :1225)
-            # :1171: 10-byte records only where forced (P < 2^26), k >= 16, and the remnant fits:
-            # 2 k - 5 <= 59 bits, and the meta of 64-read groups (6 + 1 + ibits <= 15 bits) fits its
-            # 16-bit array
+            # coarse bucket: no run or bucket comes near 5/4 of its even share, phase_count_v2's
+            # `cap` and `fcap`)
+            # phase_count_v2, `r10`: 10-byte records only where forced (P < 2^26), k >= 16, and the
+            # remnant fits: 2 k - 5 <= 59 bits, and the meta of 64-read groups (6 + 1 + ibits <= 15
+            # bits) fits its 16-bit array
             on = r10 == 1 and k >= 16
-            return EC_PATH_PARTITIONED, 2 if on else 1, 10 if on else 12  # :1299-1302
-        # declined: count_part.h's exact path (:1342-); :1394 partitioned (M <= 32 767, est / 8192 <=
-        # 2400); :1423 compact 12-byte records only if every tile was staged (lens[2] == 0,
-        # count_part.h:168), else 16-byte ones (:1431)
+            return EC_PATH_PARTITIONED, 2 if on else 1, 10 if on else 12  # phase_count_v2's stats
+        # declined: count_part.h's exact path (phase_count): partitioned (its `part`: M <= 32 767,
+        # est / 8192 <= 2400); compact 12-byte records only if every tile was staged (its `compact`:
+        # lens[2] == 0, count_part.h:168), else 16-byte ones
         return EC_PATH_PARTITIONED, 0, 12 if _tile_bytes(n, L) <= STAGE_BYTES else 16
-    # :2276 minimizer buckets for k <= WMB_MAX_K; :1942 the length they take; :1969, :2057 runs
+    # phase_count_w, `mb`: minimizer buckets for k <= WMB_MAX_K; phase_count_wpart, `if (mb)`: the
+    # length they take, and its minimizer runs
     if k <= WMB_MAX_K and L <= WMB_MAXL:
         return EC_PATH_PARTITIONED, 0, 16
-    # :2278 / :2276 hash buckets: 24-byte window records (:2057) if every 256-read tile fits the
-    # staged upsweep (count_wide.h:187 sets lens[2] otherwise; :2018), else the HBM table (:1893)
+    # phase_count_w, hash buckets: 24-byte window records (phase_count_wpart) if every 256-read tile
+    # fits the staged upsweep (count_wide.h:187 sets lens[2] otherwise; phase_count_wpart returns
+    # at `hsc.lens[2]`), else the HBM table (phase_count_w's table loop, finish_wide)
     if _tile_bytes(n, L) <= STAGE_W:
         return EC_PATH_PARTITIONED, 0, 24
     return EC_PATH_GENERAL, 0, 0
@@ -176,7 +185,7 @@ def seed_of(k, L):
 
 def short_lengths(k, n):
     """{read: length < k} of the short variant: the first read (the dispatch looks at it alone,
-    assemble.hip:1108-1116), reads on both sides of a wave tile's edge, one inside, the last"""
+    count_phase.h phase_count_v2's fast path), reads on both sides of a wave tile's edge, one inside, the last"""
     return {0: k - 1, 1: 0, 63: 1, 64: k // 2, n // 2: k - 1, n - 1: k - 2}
 
 
@@ -208,7 +217,7 @@ TWO_LENGTHS = (100, 150)
 
 def two_length_reads(k):
     """(buf, offsets): 600 reads of 100 and 150 bases, the first one (whose length the minimizer
-    buckets take for all, assemble.hip:1938-1946) among the shorter: every third read is cut"""
+    buckets take for all, count_phase.h phase_count_wpart, `if (mb)`) among the shorter: every third read is cut"""
     key = ("two", k)
     if key not in _INPUT:
         n, (la, lb) = 600, TWO_LENGTHS

@@ -1,6 +1,6 @@
 """Every compiled variant of the count kernels against the oracle: k x read length.
 
-The dispatch of csrc/assemble.hip picks a template instantiation from k and the read length L
+The dispatch of csrc/count_phase.h picks a template instantiation from k and the read length L
 (tests/kernel_grid.py restates it): k_skpart_w<NPF, W, VAL> for 21 <= k <= 32 (36 (NPF, W) pairs
 in two VAL forms), k_partition<NPF, HI, R10> (12 forms), k_wbv<W> for 33 <= k <= 52 (20 widths).
 This grid runs each of them, at the lengths where a wave's LDS stage is exactly full or steps to
@@ -81,8 +81,9 @@ def test_superkmer_grid(gpu_session, k, L):
 @pytest.mark.parametrize("k,L", kg.A_CELLS)
 def test_superkmer_grid_after_prescan(gpu_session, k, L):
     """k_skpart_w<NPF, k - 14, false>: the first read is shorter than k, so phase_count_v2 skips
-    the fast path (assemble.hip:1116), k_prescan takes the lengths of the reads with windows
-    (count_v2.h:81-87: one length) and phase_count_sk2 runs without `validate` (:1156); five more
+    the fast path (count_phase.h phase_count_v2, `L >= k && npf`), k_prescan takes the lengths of the
+    reads with windows (count_v2.h:81-87: one length) and phase_count_sk2 runs without `validate`
+    (phase_count_v2, `if (allow_sk2)`); five more
     reads of 0 .. k - 1 bases at a wave tile's edge, inside and at the end"""
     res = _run(gpu_session, k, L, short=True)
     assert res.stats.count_variant == 3 and res.stats.record_bytes == 16
@@ -130,7 +131,7 @@ def test_wide_grid(gpu_session, k, L):
 def test_wide_two_lengths_leave_the_minimizer_buckets(gpu_session, k):
     """reads of 100 and 150 bases, the first read a short one: k_wbv takes M = 100 - k + 1 windows
     a read, finds the longer reads (count_wide.h:64) and raises wbv_long, and the call is redone on
-    hash buckets (assemble.hip:2014, :2278: 24-byte records; a 256-read tile of <= 150 bases fits
+    hash buckets (count_phase.h phase_count_wpart at `mb && hsc.wbv_long`, phase_count_w: 24-byte records; a 256-read tile of <= 150 bases fits
     the staged upsweep).  k_upsweep_runs runs before the host sees the flag: it must pass over the
     longer reads, whose windows M .. 150 - k lie past their rows of the minimizer array."""
     buf, off = kg.two_length_reads(k)
