@@ -90,8 +90,14 @@ __device__ inline unsigned int sk2_bin(uint32_t y, uint32_t z, int k) {
 // A wave's flush: its cntw buffered entries counting-sorted by coarse bucket (the wave's own
 // counters, DPP scan), each bucket's run reserved on the workgroup cursor (spill records past
 // the capacity), the 16-B records built from the wave's 2-bit stage and stored as runs.
-__device__ inline uint32_t sk_bases16(const uint32_t *st, uint32_t p) {
-    return __builtin_amdgcn_alignbit(st[(p >> 4) + 1], st[p >> 4], 2 * (p & 15));
+// bases p .. p + 16 N - 1 of the 2-bit stage as N words (base p + 16 i + j at bits 2j of o[i]):
+// one address and one shift amount for all of them, the N + 1 stage words at immediate offsets
+template <int N>
+__device__ inline void sk_bases(const uint32_t *st, uint32_t p, uint32_t (&o)[N]) {
+    const uint32_t *w = st + (p >> 4);
+    const uint32_t sft = 2 * (p & 15);
+#pragma unroll
+    for (int i = 0; i < N; i++) o[i] = __builtin_amdgcn_alignbit(w[i + 1], w[i], sft);
 }
 // u8 HyperLogLog register max by CAS on the word holding it
 __device__ inline void sk_hll_put(unsigned int *s_hll, uint32_t hh) {
@@ -149,7 +155,9 @@ __device__ inline void skpart_flush(uint32_t cntw, const uint32_t *ent, uint16_t
             const uint32_t qe = hq[x / SK2_NMAX], q = x % SK2_NMAX;
             if (q <= (qe >> 16)) {
                 const uint32_t p = (qe & 0xFFFFu) + q;
-                const uint64_t K = (uint64_t)sk_bases16(st, p) | (uint64_t)sk_bases16(st, p + 16) << 32;
+                uint32_t kw[2];
+                sk_bases(st, p, kw);
+                const uint64_t K = (uint64_t)kw[0] | (uint64_t)kw[1] << 32;
                 const uint64_t krc = ~K & kmask, kfw = rev2_64(K) >> (64 - 2 * k);
                 sk_hll_put(s_hll, (uint32_t)(mix64(kfw < krc ? kfw : krc) >> 32));
             }
@@ -167,9 +175,11 @@ __device__ inline void skpart_flush(uint32_t cntw, const uint32_t *ent, uint16_t
             const uint32_t p0 = rel[lr] + w0;
             // the run's L = n1 + k bases, the sentinel at bit 2L - 32 of (y, z), zeros above
             const uint32_t sp = 2 * (n1 + (uint32_t)k) - 32, sbit = 1u << (sp & 31);
-            const uint32_t b1 = sk_bases16(st, p0 + 16), b2 = sk_bases16(st, p0 + 32);
+            uint32_t bs[3];
+            sk_bases(st, p0, bs);
+            const uint32_t b1 = bs[1], b2 = bs[2];
             uint4 o;
-            o.x = sk_bases16(st, p0);
+            o.x = bs[0];
             o.y = sp >= 32 ? b1 : (b1 & (sbit - 1u)) | sbit;
             o.z = sp >= 32 ? (b2 & (sbit - 1u)) | sbit : 0u;
             o.w = ((e >> 18) & ((1u << SK2_FBITS) - 1)) << 24 | ((rtile + lr) * M + w0);
@@ -308,7 +318,9 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
         // block 0 = m-mers 0 .. W - 1 (bases 0 .. k - 1): its suffix minima
         uint32_t S[W];
         {
-            const uint32_t x0 = sk_bases16(st, rel), x1 = sk_bases16(st, rel + 16);
+            uint32_t xw[2];
+            sk_bases(st, rel, xw);
+            const uint32_t x0 = xw[0], x1 = xw[1];
 #pragma unroll
             for (int tb = 0; tb < m - 1; tb++) push_base(tb < 16 ? (x0 >> (2 * tb)) & 3u : (x1 >> (2 * (tb - 16))) & 3u);
 #pragma unroll
@@ -341,7 +353,9 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
             // complement's code is the complement of the m bases read little-endian (base i at
             // bits 2i), one alignbit -- no second rolling register
             const uint32_t q = rel + w0 + W;
-            const uint32_t a0 = sk_bases16(st, q), a1 = sk_bases16(st, q + 16);
+            uint32_t aw[2];
+            sk_bases(st, q, aw);
+            const uint32_t a0 = aw[0], a1 = aw[1];
             const uint32_t rw0 = rs_term(w0);  // (uniform: window w0 + j's term is rw0 + rs_term(j))
             uint32_t H[W];
             uint32_t P = 0xFFFFFFFFu;  // prefix minimum of the next block so far
@@ -351,9 +365,12 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
             auto window = [&](int j) {
                 const uint32_t v = min(S[j], P);  // window w0 + j
                 const int tb = m - 1 + j;  // the rolled-in base, relative to q
-                const uint32_t b = tb < 16 ? (a0 >> (2 * tb)) & 3u : (a1 >> (2 * (tb - 16))) & 3u;
-                mf = (mf << 2) | b;  // (bits past the m-mer's 2m are dropped where it is used)
-                const uint32_t fw = mf & MMASK;
+                // mf = mf << 2 | base: the base at a word's top, then (mf : word) >> 30 -- a shift
+                // (none at tb = 15, 31) and an alignbit, where shift, bit-field extract and or were
+                // compiled as four instructions with the mask
+                const uint32_t bt = tb < 16 ? a0 << (30 - 2 * tb) : a1 << (30 - 2 * (tb - 16));
+                mf = __builtin_amdgcn_alignbit(mf, bt, 30);
+                const uint32_t fw = mf & MMASK;  // (bits past the m-mer's 2m are dropped here)
                 const uint32_t le = j == 0 ? a0 : j < 16 ? __builtin_amdgcn_alignbit(a1, a0, 2 * j) : a1 >> (2 * (j - 16));
                 const uint32_t rc = ~le & MMASK;
                 H[j] = mmer_hash(fw < rc ? fw : rc);
@@ -383,17 +400,21 @@ __global__ void __launch_bounds__(PT_THREADS) k_skpart_w(const uint8_t *__restri
                     window(j);
                 }
             }
-            // the next round's suffix minima (the block's unused tail at the read's end is never read)
+            // entries were stored over others: the call is redone.  (The clamp is a select beside
+            // the lane-0 branch, not an assignment inside it: there the compiler joined it with the
+            // divergent branch and kept cntw, and every window's clamp and address, in VGPRs)
+            if (cntw > elim - 64 && lane == 0) atomicOr(overflow, 1u);
+            cntw = min(cntw, elim - 64);
+            // the reads' last block has no successor: no suffix minima, and the flush is the tile's
+            // last, below
+            if (round + 1 == nrounds) break;
+            // the next round's suffix minima
 #pragma unroll
             for (int j = 0; j < W; j++) S[j] = H[j];
 #pragma unroll
             for (int j = W - 2; j >= 0; j--) S[j] = min(S[j], S[j + 1]);
-            if (cntw > elim - 64) {  // entries were stored over others: the call is redone
-                if (lane == 0) atomicOr(overflow, 1u);
-                cntw = elim - 64;
-            }
             // flush: the buffer may not take another round
-            if (round + 1 < nrounds && cntw > elim - 64 - 640) {
+            if (cntw > elim - 64 - 640) {
                 skpart_flush<C, FW>(cntw, ent, s_srt[wid], s_wcnt[wid], s_cur, s_base[wid], s_rel[wid], st, lane, gcap,
                                 cap, spill, M, rtile, recs, overflow, s_hll, s_hq[wid], smask ? 0xFFu : 0u, k,
                                 kmask);
